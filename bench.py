@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Throughput of the crackle encode+decode hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input: encode the
 label volume resident in HBM into .ckl bytes, then decode those bytes (resident in
 HBM) back into a label volume in HBM.  At N=1 the workload is BASELINE.json
 configs[2]: 1024x1024x512 uint32.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds
+what takes work of its own: the round-trip check, the per-kernel decode table and
+the rooflines, the reference's bytes and the CPU baseline.  --dump-outputs DIR
+writes what the last timed step returned (see dump_outputs).
 
 N>1: one process per GPU.  Under `torch.distributed.run` (RANK / WORLD_SIZE in the
 environment) this process is one rank; started plainly with --gpus N it spawns the N
@@ -62,7 +67,12 @@ def parse_args(argv=None):
                   help="voronoi: the connectomics-style volume the metric is quoted on; noise2000 / binary: the reference's adversarial "
                        "inputs (uniform-random labels in [0, 2000) / in {0, 1}: benchmarks/README.md:108-114, 193-227), reported for honesty")
   ap.add_argument("--cell", type=str, default="32x32x8", help="cell of the jittered-Voronoi generator (8x8x4: severely over-segmented, the reference's watershed benchmark, benchmarks/README.md:284-318)")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed steps, also check the round trip, time the decode kernels one by one (roofline), compare "
+                       "with the reference's bytes and time the CPU baseline; a plain run does only what the headline figure needs")
+  ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                  help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
   ap.add_argument("--sync-host-copy", action="store_true", help="the encoder call returns only when its host bytes are complete (default at N = 1: the codes' PCIe copy overlaps the decode leg and is waited for inside the step)")
   ap.add_argument("--cpu-sample-slices", type=int, default=0, help="slices of the CPU baseline's sample (0: the whole slab)")
   ap.add_argument("--config", type=str, default=None, choices=sorted(CONFIG_PRESETS),
@@ -70,6 +80,8 @@ def parse_args(argv=None):
                        "c1, c3, c4, c4pins = the fixed volumes BASELINE.json names, dealt out over --gpus ranks (strong scaling: what an 8-GPU run "
                        "of those configurations measures); explicit --shape / --dtype / --markov / --pins / --scaling still win")
   args = ap.parse_args(argv)
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be at least 1 and --warmup at least 0")
   if args.config:
     given = {a.split("=")[0] for a in (argv if argv is not None else sys.argv[1:]) if a.startswith("--")}
     for key, val in CONFIG_PRESETS[args.config].items():
@@ -363,6 +375,110 @@ def reference_manifest(name):
 
 DECODE_KERNELS_FOR_TRAFFIC = None   # filled from the stage names of the run
 
+DUMP_SAMPLE = 1 << 21     # values kept of a larger output: 16 MiB of labels (float64) + 8 MiB of stream (float32)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, np, torch, labels, binary):
+  """--dump-outputs DIR: what the last timed step handed its caller, for comparing two builds output for output.
+    labels.npy  the decoded labels of this rank's slab, (sz, sy, sx) flattened, as float64 (exact below 2^53)
+    stream.npy  the .ckl stream the encoder returned (the merged one on rank 0), its bytes as float32
+  An output of more than DUMP_SAMPLE values is sampled at DUMP_SEED-seeded positions (sorted, drawn over its
+  length), so the same arguments give the same positions from run to run."""
+  os.makedirs(out_dir, exist_ok=True)
+
+  def positions(n):
+    if n <= DUMP_SAMPLE:
+      return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+  np_dt = {torch.uint8: np.uint8, torch.uint16: np.uint16, torch.uint32: np.uint32, torch.uint64: np.uint64}[labels.dtype]
+  signed = {torch.uint16: torch.int16, torch.uint32: torch.int32, torch.uint64: torch.int64}.get(labels.dtype, labels.dtype)
+  flat = labels.view(signed).reshape(-1)
+  pos = positions(flat.numel())
+  if pos is not None:
+    flat = flat.index_select(0, torch.from_numpy(pos).to(flat.device))
+  np.save(os.path.join(out_dir, "labels.npy"), flat.cpu().numpy().view(np_dt).astype(np.float64))
+  stream = np.frombuffer(binary.view() if hasattr(binary, "view") else bytes(binary), dtype=np.uint8)
+  pos = positions(stream.size)
+  np.save(os.path.join(out_dir, "stream.npy"), (stream if pos is None else stream[pos]).astype(np.float32))
+
+
+def full_report(args, np, torch, synth, ckd, dev, dev_index, world, vol, binary, voxels_local, slab, np_dtype,
+                any_bad, stage_ms, serial_pipe, dec_pipe_ms, enc_pipe_ms, enc_kernel_ms):
+  """The fields of a --full line beyond the plain one (rank 0): the round trip, the decode and encode rooflines,
+  the reference's bytes and the CPU baseline."""
+  import hashlib
+  sx, sy, sz = slab
+  ckl_len = len(binary)
+  # algorithmic bytes of one decode of this rank's slab = label bytes written + stream bytes
+  # read (SURVEY.md section 8d: 4 B/voxel @u32 plus ~1 % for the stream)
+  alg_bytes = voxels_local * np_dtype.itemsize + ckl_len / world
+  pipe_ms = float(np.mean(dec_pipe_ms))
+  achieved = alg_bytes / (pipe_ms * 1e-3) / 1e9
+  copy_gbs = measured_copy_bandwidth(torch, dev)
+  workload_key = f"{sx}x{sy}x{sz} {np_dtype.name} markov {args.markov}"
+  kernels = [n for n in stage_ms if n.startswith("k_")]
+  traffic, traffic_per = pmc_traffic(kernels, workload_key)
+  dom = max(stage_ms, key=stage_ms.get) if stage_ms else None
+  res = {
+    "roundtrip_ok": any_bad == 0.0,
+    # the decode direction as one unit (north_star states its target for it): every kernel of one
+    # decode, first launch to last completion, HIP events on the decoder's streams
+    "roofline": {
+      "bound": "hbm",
+      "kernel": "decode pipeline: " + " + ".join(kernels),
+      "achieved": achieved,
+      "peak": HBM_PEAK_GBS,
+      "unit": "GB/s",
+      "frac": achieved / HBM_PEAK_GBS,
+      "traffic": traffic,
+      "measured_copy_GBs": copy_gbs,
+      "frac_of_measured_copy": achieved / copy_gbs,
+      "algorithmic_bytes_per_launch": alg_bytes,
+      "kernel_ms": pipe_ms,
+      "serialized_pipeline_ms": serial_pipe,
+      "decode_stage_ms": stage_ms,
+      "decode_stage_traffic": traffic_per,
+      "slowest_stage": None if dom is None else {
+        "kernel": dom, "kernel_ms": stage_ms[dom],
+        "achieved": alg_bytes / (stage_ms[dom] * 1e-3) / 1e9,
+        "frac": alg_bytes / (stage_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+      },
+    },
+  }
+  # the same figure for the encode direction as one unit: the slab's label bytes read + its stream bytes
+  # written over the encoder's device pipeline (first kernel to last, HIP events on its own streams).  Its
+  # longest kernel, the serial trail over nodes (one wavefront per slice, bound by dependent instruction
+  # latency, 44 MB of traffic), is a detail field: bytes over ITS time alone are not a roofline fraction.
+  enc_k = float(np.mean(enc_kernel_ms))
+  enc_p = float(np.mean(enc_pipe_ms))
+  if enc_p > 0:
+    res["roofline_encode"] = {
+      "bound": "hbm", "kernel": "encode pipeline (planes, trail, label stream: two streams)",
+      "achieved": alg_bytes / (enc_p * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+      "frac": alg_bytes / (enc_p * 1e-3) / 1e9 / HBM_PEAK_GBS,
+      "traffic": pmc_traffic_encode(workload_key) if (args.pins == 0 and args.data == "voronoi" and args.cell == "32x32x8") else None,
+      "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": enc_p,
+      "longest_kernel": {"kernel": "k_trail_walk", "kernel_ms": enc_k, "share_of_pipeline": (enc_k / enc_p) if enc_p > 0 else None},
+    }
+  # bytes against the reference encoder's own output at full size (sha256 of the whole stream)
+  if world == 1 and not args.pins:
+    name = f"c2_{sx}x{sy}x{sz}_u32" if (np_dtype.itemsize == 4 and args.markov == 0 and args.data == "voronoi" and args.cell == "32x32x8") else None
+    ref = reference_manifest(name) if name else None
+    if ref is not None:
+      sha = hashlib.sha256(bytes(binary.view()) if hasattr(binary, "view") else bytes(binary)).hexdigest()
+      res["bytes_match_reference"] = bool(sha == ref["sha256"] and ckl_len == ref["length"])
+      res["reference_sha256"] = ref["sha256"]
+  if not args.no_cpu_baseline:
+    ns = min(args.cpu_sample_slices, sz) if args.cpu_sample_slices > 0 else sz
+    slab_np = np.asfortranarray(synth.as_numpy_f(vol[:ns]))
+    hip_slab = None
+    if world == 1:
+      hip_slab = ckd.HipBackend(dev_index).encode(vol[:ns].contiguous(), (sx, sy, ns), False, True, args.markov, None)
+    res["cpu_baseline"] = cpu_baseline(np, slab_np, args.markov, hip_slab, whole=(ns == sz and world == 1))
+  return res
+
 
 def main():
   args = parse_args()
@@ -386,7 +502,6 @@ def main():
   if rehearsal_mode == "dry":
     return dry_run(args, world, rank)
 
-  import hashlib
   import numpy as np
   import torch
   import torch.distributed as dist
@@ -529,11 +644,17 @@ def main():
       enc_pipe_ms.append(p); enc_kernel_ms.append(k)
     session.close()
 
-  ok_local = bool(torch.equal(out.view(torch.uint8), vol.view(torch.uint8)))
+  # `out` and `binary` are what the last timed step returned; everything below that reuses `out` comes after this
+  if rank == 0 and args.dump_outputs:
+    dump_outputs(args.dump_outputs, np, torch, out, binary)
+
+  ok_local = True
+  if args.full:
+    ok_local = bool(torch.equal(out.view(torch.uint8), vol.view(torch.uint8)))
   # The timed decode leg reads each rank's resident slab stream; the stream the job RETURNS is the merged one
   # in the host buffer (async code copy, _finish, _seal): it is decoded here once, outside the timed region,
   # through the broadcast path (every rank its own z-range), and has to give the same labels.
-  if resident:
+  if args.full and resident:
     out.zero_()
     session = codec.open_decoder(binary, (sx, sy, sz))
     session.run(out)
@@ -543,7 +664,8 @@ def main():
   # one more decode with the z-chunks serialised on one stream, for the per-kernel table:
   # HIP events between the kernels on the decoder's own stream (ckl_decoder_stage_timing)
   stage_ms = {}
-  if rank == 0 or world > 1:
+  serial_pipe = None
+  if args.full and (rank == 0 or world > 1):
     os.environ["CKL_DECODE_CHUNKS"] = "1"
     session = backend.open_decoder(backend.device_stream(), 0, sz) if resident else codec.open_decoder(binary, (sx, sy, sz))
     acc = {}
@@ -567,16 +689,6 @@ def main():
     ms_per_step = total_s * 1e3 / K
     ckl_len = len(binary)
     item = np_dtype.itemsize
-    # algorithmic bytes of one decode of this rank's slab = label bytes written + stream bytes
-    # read (4 B/voxel @u32 plus ~1 % for the stream)
-    alg_bytes = voxels_local * item + ckl_len / world
-    pipe_ms = float(np.mean(dec_pipe_ms))
-    achieved = alg_bytes / (pipe_ms * 1e-3) / 1e9
-    copy_gbs = measured_copy_bandwidth(torch, dev)
-    workload_key = f"{sx}x{sy}x{sz} {np_dtype.name} markov {args.markov}"
-    kernels = [n for n in stage_ms if n.startswith("k_")]
-    traffic, traffic_per = pmc_traffic(kernels, workload_key)
-    dom = max(stage_ms, key=stage_ms.get) if stage_ms else None
     res = {
       "metric": metric_name(args),
       "value": voxels_total * K / total_s,
@@ -597,7 +709,7 @@ def main():
         "per_gpu_slab": f"{sx}x{sy}x{sz}",
         "parallelism": f"z-slab x{world}",
       },
-      "roundtrip_ok": any_bad == 0.0,
+      "full": bool(args.full),
       "compressed_bytes": ckl_len,
       "compression_ratio_pct": 100.0 * ckl_len / (voxels_total * item),
       "encode_voxels_per_s": voxels_total * K / (enc_sum_ms * 1e-3),
@@ -613,63 +725,13 @@ def main():
       # step still waits for them after the decode (all of it inside `value`)
       "encode_host_copy": "overlapped with the decode leg, completed inside the step" if overlap_copy else "inside the encoder call",
       "host_copy_wait_ms": float(np.mean(copy_wait_ms)) if copy_wait_ms else 0.0,
-      "decode_device_pipeline_ms": pipe_ms,
+      "decode_device_pipeline_ms": float(np.mean(dec_pipe_ms)),
       "encode_device_pipeline_ms": float(np.mean(enc_pipe_ms)),
       "encode_dfs_kernel_ms": float(np.mean(enc_kernel_ms)),
-      # the decode direction as one unit (north_star states its target for it): every kernel of one
-      # decode, first launch to last completion, HIP events on the decoder's streams
-      "roofline": {
-        "bound": "hbm",
-        "kernel": "decode pipeline: " + " + ".join(kernels),
-        "achieved": achieved,
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": achieved / HBM_PEAK_GBS,
-        "traffic": traffic,
-        "measured_copy_GBs": copy_gbs,
-        "frac_of_measured_copy": achieved / copy_gbs,
-        "algorithmic_bytes_per_launch": alg_bytes,
-        "kernel_ms": pipe_ms,
-        "serialized_pipeline_ms": serial_pipe,
-        "decode_stage_ms": stage_ms,
-        "decode_stage_traffic": traffic_per,
-        "slowest_stage": None if dom is None else {
-          "kernel": dom, "kernel_ms": stage_ms[dom],
-          "achieved": alg_bytes / (stage_ms[dom] * 1e-3) / 1e9,
-          "frac": alg_bytes / (stage_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        },
-      },
     }
-    # the same figure for the encode direction as one unit: the slab's label bytes read + its stream bytes
-    # written over the encoder's device pipeline (first kernel to last, HIP events on its own streams).  Its
-    # longest kernel, the serial trail over nodes (one wavefront per slice, bound by dependent instruction
-    # latency, 44 MB of traffic), is a detail field: bytes over ITS time alone are not a roofline fraction.
-    enc_k = float(np.mean(enc_kernel_ms))
-    enc_p = float(np.mean(enc_pipe_ms))
-    if enc_p > 0:
-      res["roofline_encode"] = {
-        "bound": "hbm", "kernel": "encode pipeline (planes, trail, label stream: two streams)",
-        "achieved": alg_bytes / (enc_p * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": alg_bytes / (enc_p * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        "traffic": pmc_traffic_encode(workload_key) if (args.pins == 0 and args.data == "voronoi" and args.cell == "32x32x8") else None,
-        "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": enc_p,
-        "longest_kernel": {"kernel": "k_trail_walk", "kernel_ms": enc_k, "share_of_pipeline": (enc_k / enc_p) if enc_p > 0 else None},
-      }
-    # bytes against the reference encoder's own output at full size (sha256 of the whole stream)
-    if world == 1 and not args.pins:
-      name = f"c2_{sx}x{sy}x{sz}_u32" if (np_dtype.itemsize == 4 and args.markov == 0 and args.data == "voronoi" and args.cell == "32x32x8") else None
-      ref = reference_manifest(name) if name else None
-      if ref is not None:
-        sha = hashlib.sha256(bytes(binary.view()) if hasattr(binary, "view") else bytes(binary)).hexdigest()
-        res["bytes_match_reference"] = bool(sha == ref["sha256"] and ckl_len == ref["length"])
-        res["reference_sha256"] = ref["sha256"]
-    if not args.no_cpu_baseline:
-      ns = min(args.cpu_sample_slices, sz) if args.cpu_sample_slices > 0 else sz
-      slab = np.asfortranarray(synth.as_numpy_f(vol[:ns]))
-      hip_slab = None
-      if world == 1:
-        hip_slab = ckd.HipBackend(dev_index).encode(vol[:ns].contiguous(), (sx, sy, ns), False, True, args.markov, None)
-      res["cpu_baseline"] = cpu_baseline(np, slab, args.markov, hip_slab, whole=(ns == sz and world == 1))
+    if args.full:
+      res.update(full_report(args, np, torch, synth, ckd, dev, dev_index, world, vol, binary, voxels_local, (sx, sy, sz), np_dtype,
+                             any_bad, stage_ms, serial_pipe, dec_pipe_ms, enc_pipe_ms, enc_kernel_ms))
     print(json.dumps(res), file=_json_out, flush=True)
 
   if world > 1 or group1:

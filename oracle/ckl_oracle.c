@@ -1464,7 +1464,9 @@ static int dec_run(
 	d.out = out; d.has_label = has_label; d.label = label;
 	size_t threads = 0;
 	int rc = 0;
-	if (header_bytes(h) + grid_index_bytes(h) + h->num_label_bytes + markov_model_bytes(h) + 4 * ((uint64_t)h->sz + 1) > n) {
+	/* the crc tail (labels crc + one crc per slice) exists from format version 1 on */
+	const uint64_t crc_tail = h->format_version == 0 ? 0 : 4 * ((uint64_t)h->sz + 1);
+	if (header_bytes(h) + grid_index_bytes(h) + h->num_label_bytes + markov_model_bytes(h) + crc_tail > n) {
 		snprintf(g_err, sizeof g_err, "crackle: Unable to read past end of buffer.");
 		return 1;
 	}

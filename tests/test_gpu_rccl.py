@@ -155,7 +155,7 @@ def test_bench_two_gpus_over_rccl():
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   for extra in (["--shape", "512x512x32"], ["--shape", "512x512x32", "--dtype", "uint64", "--markov", "5"], ["--shape", "256x256x16", "--pins", "1", "--markov", "5"],
                 ["--shape", "512x512x64", "--scaling", "strong"]):
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

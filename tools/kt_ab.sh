@@ -4,4 +4,4 @@
 name=$1; shift
 export CKL_LIB_AB=$name; tools/kernel_times.sh ab_$name > /dev/null 2>&1; unset CKL_LIB_AB
 tools/kernel_times.sh ab_cur > /dev/null 2>&1
-for k in "$@"; do echo "$k: $(grep $k gpurun_out/ab_${name}_kt.txt | head -1 | sed "s/.*avg//") | $(grep $k gpurun_out/ab_cur_kt.txt | head -1 | sed "s/.*avg//")"; done
+for k in "$@"; do echo "$k: $(grep $k tool_out/ab_${name}_kt.txt | head -1 | sed "s/.*avg//") | $(grep $k tool_out/ab_cur_kt.txt | head -1 | sed "s/.*avg//")"; done

@@ -1,12 +1,13 @@
 #!/bin/bash
 # bench.py on the other BASELINE.json configurations (one GPU's slab each), on the reference's adversarial inputs and on
 # over-segmented volumes (its watershed benchmark), the last two groups with the compiled reference timed on the box's
-# host cores beside them -> gpurun_out/other_configs.txt
-out=gpurun_out/other_configs.txt
+# host cores beside them -> tool_out/other_configs.txt
+mkdir -p tool_out
+out=tool_out/other_configs.txt
 : > $out
 run() {
   name=$1; shift
-  python3 bench.py --steps 5 --warmup 2 "$@" 2>gpurun_out/other_configs.err | python3 -c "
+  python3 bench.py --full --steps 5 --warmup 2 "$@" 2>tool_out/other_configs.err | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 cpu = d.get('cpu_baseline')

@@ -3,9 +3,9 @@
 /opt/skills/guides/MI355X_MICROARCH.md, HBM / PMC slots) of `bench.py` into
 profiles/r03_pmc_traffic.json: memory-side bytes per launch of every ckl kernel.
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-  python3 tools/pmc_summary.py gpurun_out/pmc_fetch gpurun_out/pmc_write "1024x1024x512 uint32 markov 0" profiles/r03_pmc_traffic.json
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d tool_out/pmc_fetch -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d tool_out/pmc_write -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
+  python3 tools/pmc_summary.py tool_out/pmc_fetch tool_out/pmc_write "1024x1024x512 uint32 markov 0" profiles/r03_pmc_traffic.json
 
 Units and corrections (the guide's HBM section): both counters are reported in KiB
 (TCC_EA0_RDREQ / WRREQ scaled by the request size); on gfx950 FETCH_SIZE tallies the
@@ -75,7 +75,7 @@ def main():
   res = {
     "workload": workload,
     "lib_sha16": sha16,      # digest of the library's sources: bench.py takes roofline.traffic from this file only while they are unchanged
-    "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of bench.py --steps 1 --warmup 1",
+    "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of bench.py --full --steps 1 --warmup 1",
     "correction": "bytes = (2 x FETCH_SIZE + WRITE_SIZE) KiB: gfx950 counts 128-byte read requests at 64 bytes",
     "kernels": kernels,
   }

@@ -25,7 +25,7 @@ def bench(extra, group1):
     env["CKL_PROFILE"] = "1"      # the sharded encoder's stage times on stderr (rank 0's pin section is read from them)
   else:
     env.pop("CKL_BENCH_REHEARSAL", None)
-  cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "5", "--warmup", "2"] + extra
+  cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "5", "--warmup", "2"] + extra
   r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
   if r.returncode != 0:
     raise RuntimeError(" ".join(cmd) + "\n" + r.stderr[-1500:])

@@ -580,13 +580,11 @@ std::vector<uint8_t> pins_cover_host(
 	}
 	parallel_sort(all_labels.begin(), all_labels.end(), [](const std::pair<uint64_t, uint32_t>& a, const std::pair<uint64_t, uint32_t>& b) { return a.first < b.first; });
 
-	const int num_pins_width = byte_width(max_pins);
 	const int depth_width = byte_width(max_depth);
 	const int cc_label_width = byte_width(n_total);
 	const int component_width = byte_width(sxy);
 	const uint8_t pin_bytes = static_cast<uint8_t>(index_width + depth_width);
 	const uint8_t cc_efficient_threshold = static_cast<uint8_t>(pin_bytes / cc_label_width);
-	const uint8_t combined = static_cast<uint8_t>(ilog2w(num_pins_width) | (ilog2w(depth_width) << 2) | (ilog2w(cc_label_width) << 4));
 
 	std::vector<uint8_t> bin;
 	put_le(bin, bgcolor, stored_width);
@@ -594,11 +592,10 @@ std::vector<uint8_t> pins_cover_host(
 	bin.reserve(bin.size() + all_labels.size() * static_cast<size_t>(stored_width) + static_cast<size_t>(sz) * component_width + 1);
 	for (const auto& kv : all_labels) put_le(bin, kv.first, stored_width);
 	for (int64_t z = 0; z < sz; z++) put_le(bin, ncomp[z], component_width);
-	bin.push_back(combined);
 
 	// the labels' records are independent: sized first, then written side by side at their places
 	const size_t n_rec = all_labels.size();
-	std::vector<uint64_t> rec_at(n_rec + 1, 0);
+	std::vector<uint64_t> rec_at(n_rec + 1, 0), n_ids_of(n_rec, 0);
 	parallel_for(n_rec, 256, [&](size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; i++) {
 			const uint32_t li = all_labels[i].second;
@@ -609,10 +606,20 @@ std::vector<uint8_t> pins_cover_host(
 				if (depth_of(p) >= cc_efficient_threshold) n_repr++;
 				else n_ids += ids_off[p + 1] - ids_off[p];
 			}
-			rec_at[i + 1] = 2ull * num_pins_width + n_repr * static_cast<uint64_t>(index_width + depth_width) + n_ids * static_cast<uint64_t>(cc_label_width);
+			rec_at[i + 1] = n_repr * static_cast<uint64_t>(index_width + depth_width) + n_ids * static_cast<uint64_t>(cc_label_width);
+			n_ids_of[i] = n_ids;
 		}
 	});
-	for (size_t i = 0; i < n_rec; i++) rec_at[i + 1] += rec_at[i];
+	// A record holds two counts in num_pins_width bytes each: its pins and its single-component ids.  The reference sizes
+	// the field from the pin counts alone (labels.hpp:209-229), so a label with more than 255 ids beside fewer than 256 pins
+	// per label overflows the count and the section cannot be decoded (tools/repro_pins_u8.py).  Here the field holds both;
+	// where every count fits in the pins' width the bytes are the reference's.
+	uint64_t max_ids = 0;
+	for (size_t i = 0; i < n_rec; i++) max_ids = std::max(max_ids, n_ids_of[i]);
+	const int num_pins_width = byte_width(std::max(max_pins, max_ids));
+	const uint8_t combined = static_cast<uint8_t>(ilog2w(num_pins_width) | (ilog2w(depth_width) << 2) | (ilog2w(cc_label_width) << 4));
+	bin.push_back(combined);
+	for (size_t i = 0; i < n_rec; i++) rec_at[i + 1] += rec_at[i] + 2ull * num_pins_width;
 	const size_t head_bytes = bin.size();
 	bin.resize(head_bytes + rec_at[n_rec]);
 	struct Sorted { uint64_t idx, depth; uint32_t pin; };

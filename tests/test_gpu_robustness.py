@@ -72,18 +72,27 @@ def test_overrides_that_force_nothing_use_the_cached_volume_statistics(checker):
 
 
 @pytest.mark.gpu
-def test_the_references_overflowed_pin_section_is_refused(checker):
+def test_overflowing_pin_counts_are_widened_and_the_references_section_refused(checker):
   """The reference's pin encoder writes the count of a label's single-component ids in a field sized from the labels' pin
   counts (src/labels.hpp:209-229): 1024 x 248 x 4 uint8 voxels of 4 x 4 x 2 cells give a label 261 such ids beside fewer
   than 256 pins per label, the one-byte count overflows and the reference decodes its own stream to wrong labels
-  (tools/repro_pins_u8.py).  The encoder here writes the same bytes (bit-exact); the decoder refuses them."""
+  (tools/repro_pins_u8.py).  The decoder refuses those bytes.  The encoder here sizes the count field from the id counts
+  too: its stream differs from the reference's only in two-byte counts, and every decoder reads it back to the input."""
   shape = (1024, 248, 4)
   arr = synth.as_numpy_f(synth.voronoi_labels(shape, np.uint8, seed=11, cell=(4, 4, 2)))
   want = checker.compress(arr, allow_pins=True)
-  assert crackle_amd.compress(arr, allow_pins=True) == want
   with pytest.raises(RuntimeError, match="pin section is malformed"):
     crackle_amd.decompress(want)
-  # one slice less and every count fits: the same geometry round-trips
+  got = crackle_amd.compress(arr, allow_pins=True)
+  assert got != want
+  head = crackle_amd.header(got)
+  sec = got[head.header_bytes + head.grid_index_bytes:][:head.num_label_bytes]
+  n = int.from_bytes(sec[1:9], "little")
+  combined = sec[1 + 8 + n + 4 * shape[2]]      # uint8 labels, 4-byte component counts (sx * sy > 65535)
+  assert 1 << (combined & 3) == 2, "num_pins_width"
+  assert np.array_equal(crackle_amd.decompress(got), arr)
+  assert np.array_equal(checker.decompress(got).reshape(shape, order="F"), arr)
+  # one slice less and every count fits: the same geometry round-trips, byte for byte the reference's stream
   arr3 = np.asfortranarray(arr[:, :, :3])
   want3 = checker.compress(arr3, allow_pins=True)
   assert crackle_amd.compress(arr3, allow_pins=True) == want3

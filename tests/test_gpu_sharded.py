@@ -45,6 +45,13 @@ def _volume(kind):
     v[5:11, 7:12, 1] = (1 << 63) + 5
     v[200:260, 30:33, 6] = (1 << 64) - 1
     return v
+  if kind == "pin_counts":
+    # 392 single-component ids of a label beside fewer than 256 pins per label: two-byte counts (the reference writes
+    # one-byte counts that overflow); the pillars cross the slab boundary
+    v = np.zeros((128, 128, 4), np.uint8, order="F")
+    v[::9, ::9, 1:3] = 1
+    v[4::9, 4::9, 1:3] = 2
+    return v
   if kind == "c4":
     # C4's slice shape: 2048 x 2048 (x_width = y_width = 2, component_width = 4)
     return synth.as_numpy_f(synth.voronoi_labels((2048, 2048, 4), np.uint32, seed=45, cell=(32, 32, 8), device=dev))
@@ -61,6 +68,7 @@ CASES = [
   ("voronoi", 0, True, "CKL_TEST_NO_COLLECT"), ("u64", 5, True, "CKL_TEST_NO_COLLECT"), ("c4", 5, True, "CKL_TEST_NO_COLLECT"),
   # ... unless asked for, or when the chosen pins' id lists pass their budget (here: one entry)
   ("voronoi", 5, True, "CKL_PINS_ON_ROOT"), ("voronoi", 0, True, "CKL_PIN_IDS_BUDGET"),
+  ("pin_counts", 0, True, None), ("pin_counts", 0, True, "CKL_TEST_NO_COLLECT"),
 ]
 ENVS = ("CKL_SHARDED_LEGACY", "CKL_TEST_MERGE_FAIL", "CKL_TEST_NO_COLLECT", "CKL_PINS_ON_ROOT", "CKL_PIN_IDS_BUDGET")
 
@@ -137,6 +145,11 @@ def test_sharded_hip_backend_equals_whole_volume(checker, sharded_results, index
     assert sharded_results[(rank, index)][2] is None, sharded_results[(rank, index)][2]
   vol = _volume(kind)
   whole = checker.compress(vol, markov_model_order=order, allow_pins=pins)
+  if kind == "pin_counts":
+    # the checker's stream overflows its counts: the single-process stream instead, read back by the checker
+    import crackle_amd
+    whole = crackle_amd.compress(vol, allow_pins=True)
+    assert np.array_equal(checker.decompress(whole).reshape(vol.shape, order="F"), vol)
   assert sharded_results[(0, index)][0] == whole, "merged slab streams differ from the whole-volume stream"
   assert sharded_results[(1, index)][0] is None
   assert sharded_results[(0, index)][1] and sharded_results[(1, index)][1], "a rank decoded its z-range wrongly"

@@ -104,3 +104,43 @@ def test_pin_host_argument_checks():
   nc = np.ones(1, np.uint32)
   assert L.ckl_pin_labels_host(a.ctypes.data, 3, c.ctypes.data, 2, 2, 1, nc.ctypes.data, 1, 1, 0, C.byref(out), C.byref(n)) != 0
   assert "dtype" in _lib.last_error()
+
+
+def _bw(x):
+  return 1 if x <= 0xFF else 2 if x <= 0xFFFF else 4 if x <= 0xFFFFFFFF else 8
+
+
+def test_id_count_widens_the_count_field(checker):
+  """A label with more than 255 single-component ids beside fewer than 256 pins per label: 2-slice pillars of two
+  labels, the one with more pins is the background colour, the other keeps 196 pins of depth 1 written as 392 ids.
+  The reference sizes both counts of a record from the pin counts alone (one byte here) and its section overflows;
+  the section written here takes its count width from the ids too (2 bytes) and its records end with it."""
+  L = _lib.lib()
+  arr = np.zeros((128, 128, 4), np.uint8, order="F")
+  arr[::9, ::9, 0:2] = 1
+  arr[4::9, 4::9, 0:2] = 2
+  sec = _pin_section(L, checker, arr)
+  sw = 1
+  n = int.from_bytes(sec[sw:sw + 8], "little")
+  p = sw + 8 + sw * n + _bw(128 * 128) * 4
+  combined = sec[p]
+  p += 1
+  npw, dw, ccw = 1 << (combined & 3), 1 << ((combined >> 2) & 3), 1 << ((combined >> 4) & 3)
+  iw = _bw(128 * 128 * 4)
+  assert (npw, dw, ccw, iw) == (2, 1, 2, 4)
+  most_ids = 0
+  for _ in range(n):
+    pins = int.from_bytes(sec[p:p + npw], "little")
+    p += npw + pins * (iw + dw)
+    ids = int.from_bytes(sec[p:p + npw], "little")
+    p += npw + ids * ccw
+    assert p <= len(sec)
+    most_ids = max(most_ids, ids)
+  assert p == len(sec), "the records do not end with the section"
+  assert most_ids == 392
+  # the reference's section of the same volume has one-byte counts (combined byte: 1 / 1 / 2) and is one byte per
+  # record shorter than the records it claims
+  want = _want_section(checker, arr)
+  assert want is not None and want[:1 + 8 + n + 2 * 4] == sec[:1 + 8 + n + 2 * 4]
+  assert want[1 + 8 + n + 2 * 4] == 0b010000 and combined == 0b010001
+  assert len(want) == len(sec) - 2 * n

@@ -7,9 +7,11 @@ whose labels all have fewer than 256 pins overflows that one-byte count: the ref
 decoder parses out of step, and crackle.decompress(crackle.compress(x, allow_pins=True)) != x.  It takes few label values
 with many small components each: uint8 volumes of tiny Voronoi cells two slices deep, 1024 x 244 ... 256 x 4.
 
-crackle_amd's encoder is bit-exact against the reference's (the requirement), so it writes the same bytes, and its decoder,
-like the reference's, returns wrong labels for them.  This script shows both: our bytes equal the reference's, the reference
-decodes its own stream wrongly, and where the count field overflows.  (Run on a GPU box; the first half needs none.)"""
+crackle_amd's encoder sizes the count field from the id counts too (ckl_pins.hip, pins_cover_host): where every count
+fits in the pins' width its bytes are the reference's; where one does not, its counts are wider and every decoder reads
+the stream back to the input.  Its decoder refuses the reference's overflowed sections (their records do not end with the
+section) instead of returning labels read out of step.  This script shows where the reference's count field overflows, the
+reference decoding its own stream wrongly, and crackle_amd's stream differing from it and round-tripping.  (Run on a GPU box; the first half needs none.)"""
 import sys
 import numpy as np
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
@@ -69,6 +71,7 @@ try:
     line += f"; our decode {'correct' if np.array_equal(back, arr) else 'wrong (%d voxels)' % int((back != arr).sum())}"
   except RuntimeError as exc:
     line += f"; our decoder refuses the stream: {str(exc)[:90]}"
+  line += f"; our stream round-trips: {np.array_equal(crackle_amd.decompress(got), arr)}"
 except (OSError, ImportError) as exc:      # no GPU here
   line += f"; (HIP path not run: {type(exc).__name__})"
 print(line, flush=True)

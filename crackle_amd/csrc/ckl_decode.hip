@@ -2691,7 +2691,8 @@ void decoder_build(ckl_decoder& d, const uint8_t* buf, uint64_t n, int64_t z_sta
 	d.sxy = static_cast<uint64_t>(h.sx) * h.sy;
 	d.n_bytes = n;
 	if (d.sxy == 0) return;
-	if (d.sxy >= (1ull << 31)) throw Error(CKL_ERR_ARG, "crackle_amd: slices of 2^31 or more pixels are not supported");
+	// the encoder's limit (check_dims, ckl_encode.hip): slices of 2^30 or more pixels are not decoded correctly
+	if ((static_cast<uint64_t>(h.sx) + 1) * (static_cast<uint64_t>(h.sy) + 1) >= (1ull << 30)) throw Error(CKL_ERR_ARG, "crackle_amd: slices of 2^30 or more crack vertices are not supported");
 
 	const uint64_t hb = h.header_bytes(), gib = h.grid_index_bytes();
 	const uint64_t tail = h.format_version == 0 ? 0 : 4ull * (static_cast<uint64_t>(h.sz) + 1);

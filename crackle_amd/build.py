@@ -48,9 +48,8 @@ TUNING_LIB = os.path.join(HERE, "libcrackle_amd_tuning.so")
 
 
 def build(force=False, verbose=True, tuning=False):
-  """tuning=True builds libcrackle_amd_tuning.so with -DCKL_TUNING (in-kernel cycle stamps and the
-  ablation switches of tools/ablate.sh; selected at run time with CKL_TUNING_LIB=1).  The shipped
-  library has neither."""
+  """tuning=True builds libcrackle_amd_tuning.so with -DCKL_TUNING (in-kernel cycle stamps; selected
+  at run time with CKL_TUNING_LIB=1).  The shipped library has none."""
   srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
   hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
   objdir = os.path.join(HERE, "build_tuning" if tuning else "build")

@@ -254,10 +254,7 @@ struct RecArgs {
 	uint32_t lds_bytes;
 	WordRec* words;              // [word_base[zi] + word]
 	const uint64_t* word_base;   // [nslices]
-	uint32_t* fused_ctl;         // k_strip_fused's words (fused_ctl_words of ticket counters and timeout, arrive[fused_n], ready[fused_n]): zeroed here, or null
-	uint32_t fused_n, fused_ctl_words;
 	unsigned long long* diag;    // tuning builds: cycle stamps, summed over the slices
-	uint32_t ablate;             // tuning builds (CKL_ABLATE, results wrong): 0x400000 no parked-word stores, 0x800000 the parked words are loaded and dropped, 0x1000000 they are not loaded
 };
 
 // the seldom-taken parts of k_crack_match (as functions of their own, not inlined, they made the kernel
@@ -602,7 +599,7 @@ __global__ void __launch_bounds__(BLOCK, 4) k_crack_match(RecArgs ra) {
 					else if (o_a + 2u < kcap) { a.g_kind[kb + o_a] = static_cast<uint8_t>(kind); a.g_dx[kb + o_a] = cp; }
 					o_a++;
 				}
-				if (j < words_per && !(kTuning && (ra.ablate & 0x400000u))) *reinterpret_cast<uint4*>(wout + w0 + j * BLOCK) = make_uint4(w.prevs, w.ms | (w.isT << 1), o_p, o_t);
+				if (j < words_per) *reinterpret_cast<uint4*>(wout + w0 + j * BLOCK) = make_uint4(w.prevs, w.ms | (w.isT << 1), o_p, o_t);
 				o_t += __popc(w.isT);
 				o_p += __popc(mR) - __popc(mL) + ((__popc(mD) - __popc(mU)) << 16);
 			}
@@ -656,10 +653,8 @@ __global__ void __launch_bounds__(BLOCK, 4) k_crack_match(RecArgs ra) {
 #pragma unroll
 				for (uint32_t q = 0; q < kBatch; q++) {
 					const uint32_t w = w0 + q * BLOCK + tid;
-					if (kTuning && (ra.ablate & 0x1000000u)) { wr[q] = make_uint4(0u, 0u, 0u, 0u); continue; }
 					wr[q] = load_word(w < n_words ? w : 0u);
 					if (w >= n_words) wr[q].y = 0u;
-					if (kTuning && (ra.ablate & 0x800000u)) wr[q].y = 0u;
 				}
 				// The batch's words side by side, step by step — segment offset (LDS), start vertex and strips, a slot from the
 				// strip's cursor (LDS atomic), the store: done word by word, each behind its own branches, a thread went
@@ -726,12 +721,7 @@ __global__ void __launch_bounds__(BLOCK, 4) k_crack_match(RecArgs ra) {
 	if (tid == 0) {
 		a.slice_err[zi] = s_err;      // later kernels of the decode OR their bits in
 		if (a.overflow && blockIdx.x == 0 && a.zbase == 0) *a.overflow = 0u;      // the strip kernels' overflow word (this is the first kernel of the decode)
-		if (ra.fused_ctl) {      // the next launch's ticket / arrival / ready words (a kernel boundary lies between)
-			ra.fused_ctl[ra.fused_ctl_words + zi] = 0u;
-			ra.fused_ctl[ra.fused_ctl_words + ra.fused_n + zi] = 0u;
-		}
 	}
-	if (ra.fused_ctl && blockIdx.x == 0) for (uint32_t w = tid; w < ra.fused_ctl_words; w += BLOCK) ra.fused_ctl[w] = 0u;      // ticket counters, timeout
 	if (kTuning && dgp && tid < 32 && s_dg[tid]) atomicAdd(ra.diag + tid, s_dg[tid]);
 }
 

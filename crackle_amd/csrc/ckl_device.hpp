@@ -9,8 +9,7 @@ namespace ckl {
 namespace dev {
 
 // Tuning builds (-DCKL_TUNING, `python -m crackle_amd.build --tuning` -> libcrackle_amd_tuning.so) keep the
-// in-kernel cycle stamps (CKL_*_DIAG) and the ablation switches (CKL_ABLATE: parts of kernels skipped,
-// results wrong); the shipped library compiles both out.
+// in-kernel cycle stamps (CKL_*_DIAG); the shipped library compiles them out.
 #ifdef CKL_TUNING
 constexpr bool kTuning = true;
 #else

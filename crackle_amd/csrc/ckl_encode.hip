@@ -145,117 +145,10 @@ __device__ __forceinline__ V nt_load_vec(const T* p) {
 	return v;
 }
 
-template <typename LABEL>
-__global__ void __launch_bounds__(kBlock) k_label_planes_fast(
-	const LABEL* __restrict__ labels, uint32_t sx, uint32_t sy, uint32_t strips, uint32_t bands,
-	uint32_t* __restrict__ planeV, uint32_t* __restrict__ planeH, uint32_t row_words, uint64_t plane_words,
-	uint32_t* __restrict__ partial /* [nslices][gridDim.x][4]: nv, nh, pairs, - */, unsigned long long* __restrict__ partial_max,
-	unsigned long long* __restrict__ total_pairs /* zeroed here, summed by k_planes_reduce behind this kernel */
-) {
-	if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *total_pairs = 0;
-	constexpr uint32_t P = 16 / sizeof(LABEL);        // pixels per lane
-	constexpr uint32_t G = 32 / P;                    // lanes per plane word
-	struct alignas(16) Vec { LABEL v[P]; };
-	__shared__ uint32_t s_red[3 * kWaves];
-	__shared__ unsigned long long s_max[kWaves];
-	const uint32_t zi = blockIdx.y;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const uint32_t task = blockIdx.x * kWaves + wave;
-	uint32_t nv = 0, nh = 0, pairs = 0;
-	LABEL mxl = 0;      // (in the label's own width: a 64-bit compare + select per pixel was a tenth of the kernel's VALU work)
-	if (task < strips * bands) {
-		const uint32_t band = task / strips, strip = task - band * strips;
-		const uint32_t x = strip * (64u * P) + lane * P;
-		const uint32_t y0 = band * kBandRows, y1 = min(y0 + kBandRows, sy);
-		const bool active = x < sx;
-		const uint64_t slice_off = static_cast<uint64_t>(zi) * sy * sx;
-		const LABEL* col = labels + slice_off + x;
-		Vec prev;
-#pragma unroll
-		for (uint32_t i = 0; i < P; i++) prev.v[i] = 0;
-		if (active && y0 > 0) prev = *reinterpret_cast<const Vec*>(col + static_cast<uint64_t>(y0 - 1) * sx);
-		uint32_t* pv = planeV + zi * plane_words;
-		uint32_t* ph = planeH + zi * plane_words;
-		const uint32_t word = (x >> 5);
-		// kRowsAhead rows are loaded before the first of them is compared: one 16-byte load per
-		// lane in flight does not cover the memory latency at the occupancy the CU allows
-		constexpr uint32_t kRowsAhead = 4;
-		for (uint32_t yb = y0; yb < y1; yb += kRowsAhead) {
-			Vec rows[kRowsAhead];
-			LABEL edges[kRowsAhead];
-			bool have_edges[kRowsAhead];
-#pragma unroll
-			for (uint32_t r = 0; r < kRowsAhead; r++) {
-				const uint32_t y = yb + r;
-				edges[r] = 0; have_edges[r] = false;
-				if (active && y < y1) {
-					rows[r] = nt_load_vec<Vec>(col + static_cast<uint64_t>(y) * sx);      // read once: non-temporal (7.0 against 6.2 TB/s in a pure read, tools/micro/load_bw.hip)
-					if (lane == 0) {
-						// linear predecessor of the strip's first pixel (previous row / slice when x == 0)
-						const uint64_t lin = slice_off + static_cast<uint64_t>(y) * sx + x;
-						if (lin > 0) { edges[r] = labels[lin - 1]; have_edges[r] = true; }
-					}
-				}
-				else rows[r] = prev;
-			}
-#pragma unroll
-			for (uint32_t r = 0; r < kRowsAhead; r++) {
-				const uint32_t y = yb + r;
-				if (y >= y1) break;
-				const Vec cur = active ? rows[r] : prev;
-				LABEL left = __shfl_up(cur.v[P - 1], 1, kWave);
-				bool have_left = true;
-				if (lane == 0) { left = edges[r]; have_left = have_edges[r]; }
-				uint32_t bv = 0, bh = 0;
-				if (active) {
-					// bit i: pixel i differs from its left / upper neighbour; the border cases (no left neighbour at
-					// the volume's first voxel, x == 0, y == 0) are masked once per row instead of tested per pixel
-#pragma unroll
-					for (uint32_t i = 0; i < P; i++) {
-						const LABEL l = i ? cur.v[i - 1] : left;
-						bv |= (cur.v[i] != l ? 1u : 0u) << i;
-						bh |= (cur.v[i] != prev.v[i] ? 1u : 0u) << i;
-						mxl = cur.v[i] > mxl ? cur.v[i] : mxl;
-					}
-					// lib::pixel_pairs counts equal LINEAR neighbours (lib.hpp:249-256): every pixel but the volume's first has one
-					pairs += P - __popc(bv) - ((have_left || (bv & 1u)) ? 0u : 1u);
-					if (x == 0) bv &= ~1u;      // no crack along the image's left border
-					if (y == 0) bh = 0u;
-				}
-				nv += __popc(bv); nh += __popc(bh);
-				bv <<= (lane % G) * P; bh <<= (lane % G) * P;
-#pragma unroll
-				for (uint32_t sft = 1; sft < G; sft <<= 1) {
-					bv |= __shfl_xor(bv, sft, kWave);
-					bh |= __shfl_xor(bh, sft, kWave);
-				}
-				if ((lane % G) == 0 && word < row_words && active) {
-					pv[static_cast<uint64_t>(y) * row_words + word] = bv;
-					ph[static_cast<uint64_t>(y) * row_words + word] = bh;
-				}
-				prev = cur;
-			}
-		}
-	}
-	nv = wave_sum(nv); nh = wave_sum(nh); pairs = wave_sum(pairs);
-	unsigned long long mx = static_cast<unsigned long long>(mxl);
-	for (int d = kWave / 2; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(mx, d, kWave); mx = o > mx ? o : mx; }
-	if (lane == 0) { s_red[wave] = nv; s_red[kWaves + wave] = nh; s_red[2 * kWaves + wave] = pairs; s_max[wave] = mx; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t tv = 0, th = 0, tp = 0;
-		unsigned long long tm = 0;
-		for (int w = 0; w < kWaves; w++) { tv += s_red[w]; th += s_red[kWaves + w]; tp += s_red[2 * kWaves + w]; tm = s_max[w] > tm ? s_max[w] : tm; }
-		const uint64_t o = static_cast<uint64_t>(zi) * gridDim.x + blockIdx.x;
-		partial[o * 4 + 0] = tv; partial[o * 4 + 1] = th; partial[o * 4 + 2] = tp; partial[o * 4 + 3] = 0;
-		partial_max[o] = tm;
-	}
-}
-
-// The same pass with nothing but label loads in the wavefront's memory queue (round 5).  k_label_planes_fast stores two
-// plane words per row from inside its row loop; loads and stores retire on ONE counter on this architecture and
-// "mixed" means "wait for all": every group of four rows drained its stores before the next loads went out, and the
-// kernel read 2.15 GB in 0.42 - 0.46 ms where a plain read takes 0.31.  Here a row's plane words go to LDS (2 KiB per
+// The label-planes pass with nothing but label loads in the wavefront's memory queue (round 5).  Round 1's kernel
+// (since removed) stored two plane words per row from inside its row loop; loads and stores retire on ONE counter on
+// this architecture and "mixed" means "wait for all": every group of four rows drained its stores before the next
+// loads went out, and that kernel read 2.15 GB in 0.42 - 0.46 ms where a plain read takes 0.31.  Here a row's plane words go to LDS (2 KiB per
 // wavefront for a strip of 32 rows) and leave in two 16-byte stores per lane after the loop; the label of the pixel left
 // of the strip is a SCALAR load (its own counter); and the rows sit in a window of kRowsAhead registers that is
 // refilled as it is consumed, so that kRowsAhead - 1 row loads are always in flight.
@@ -878,7 +771,7 @@ __global__ void __launch_bounds__(kBlock) k_paint_components4(
 inline void launch_paint_components(hipStream_t s, const uint32_t* planeV, uint32_t row_words, uint64_t plane_words, int64_t sx, int64_t sy, int64_t sz,
 	const uint32_t* word_base, const uint64_t* rbase, const uint32_t* run_cc, const uint64_t* comp_off, uint32_t id_base, uint32_t* out) {
 	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	const bool four = sx % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0 && !getenv("CKL_PAINT_COMPONENTS_1");
+	const bool four = sx % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
 	const uint64_t threads = four ? sxy / 4 : sxy;
 	const dim3 grid(static_cast<uint32_t>((threads + kBlock - 1) / kBlock), static_cast<uint32_t>(sz));
 	if (four) hipLaunchKernelGGL(k_paint_components4, grid, dim3(kBlock), 0, s, planeV, row_words, plane_words, static_cast<uint32_t>(sx), sxy, word_base, rbase, run_cc, comp_off, id_base, out);
@@ -1263,8 +1156,6 @@ static void copy_bytes_device(const uint8_t* src, uint8_t* dst, uint64_t n, hipS
 	hipLaunchKernelGGL(k_copy_bytes, dim3(blocks), dim3(kBlock), 0, s, src, dst, n);
 }
 
-constexpr uint32_t kTrailStreams = 8;
-
 struct VolumeStats { uint64_t max_label = 0, pairs = 0, first = 0, last = 0; };
 
 struct ckl_encoder {
@@ -1272,11 +1163,9 @@ struct ckl_encoder {
 	hipStream_t stream = nullptr;      // crack codes
 	hipStream_t stream2 = nullptr;     // labels (components, crcs, label table), concurrent with the crack trail
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, evk0 = nullptr, evk1 = nullptr, ev_in = nullptr;
-	hipEvent_t evd0 = nullptr, evd1 = nullptr;      // around k_trail_walk (first slice group)
+	hipEvent_t evd0 = nullptr, evd1 = nullptr;      // around k_trail_walk
 	float trail_ms = 0.f;
-	hipStream_t trail_stream[kTrailStreams] = {};     // slice groups of the crack trail
 	hipEvent_t ev_prezero = nullptr;   // trail_prezero()'s fills on stream2 are done
-	hipEvent_t ev_fork = nullptr, ev_join[kTrailStreams] = {}, ev_pre[kTrailStreams] = {};      // ev_pre[g]: group g's kernels in front of its walk are done
 	float pipeline_ms = 0.f, dominant_ms = 0.f;
 	int64_t max_sx = 0, max_sy = 0, max_sz = 0;
 	int dtype_bytes = 0;
@@ -1370,11 +1259,7 @@ struct ckl_encoder {
 		if (evd0) (void)hipEventDestroy(evd0);
 		if (evd1) (void)hipEventDestroy(evd1);
 		if (ev_in) (void)hipEventDestroy(ev_in);
-		if (ev_fork) (void)hipEventDestroy(ev_fork);
 		if (ev_prezero) (void)hipEventDestroy(ev_prezero);
-		for (auto& ev : ev_join) if (ev) (void)hipEventDestroy(ev);
-		for (auto& ev : ev_pre) if (ev) (void)hipEventDestroy(ev);
-		for (auto& st : trail_stream) if (st) (void)hipStreamDestroy(st);
 		if (stream) (void)hipStreamDestroy(stream);
 		if (stream2) (void)hipStreamDestroy(stream2);
 		if (stream_copy) { (void)hipStreamSynchronize(stream_copy); (void)hipStreamDestroy(stream_copy); }
@@ -1534,19 +1419,15 @@ void planes_pass(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, in
 		e.d_plane_partial.ensure(4ull * nblk * ns);
 		e.d_plane_partial_max.ensure(static_cast<size_t>(nblk) * ns);
 		e.d_plane_out.ensure(4ull * ns + 1);
-		if (!getenv("CKL_NO_PREZERO")) trail_prezero(e, sx, sy, sz);
-		if (!getenv("CKL_PLANES_V1")) hipLaunchKernelGGL(k_label_planes_stream<LABEL>, dim3(nblk, ns), dim3(kBlock), 0, s,
-			labels, static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), strips, bands,
-			e.d_planes.p, e.d_planes.p + e.plane_words * ns, e.row_words, e.plane_words,
-			e.d_plane_partial.p, e.d_plane_partial_max.p, e.d_plane_out.p + 4ull * ns);
-		else hipLaunchKernelGGL(k_label_planes_fast<LABEL>, dim3(nblk, ns), dim3(kBlock), 0, s,
+		trail_prezero(e, sx, sy, sz);
+		hipLaunchKernelGGL(k_label_planes_stream<LABEL>, dim3(nblk, ns), dim3(kBlock), 0, s,
 			labels, static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), strips, bands,
 			e.d_planes.p, e.d_planes.p + e.plane_words * ns, e.row_words, e.plane_words,
 			e.d_plane_partial.p, e.d_plane_partial_max.p, e.d_plane_out.p + 4ull * ns);
 		hipLaunchKernelGGL(k_planes_reduce, dim3(ns), dim3(kBlock), 0, s, e.d_plane_partial.p, e.d_plane_partial_max.p, nblk, e.d_plane_out.p, e.d_plane_out.p + 4ull * ns);
 		// deferred: graph_pass fetches the counts together with its own (k_trail_graph decides the crack
 		// format from the device's pair count: one host round trip less in front of it)
-		e.planes_deferred = defer && !getenv("CKL_NO_DEFER");
+		e.planes_deferred = defer;
 		if (!e.planes_deferred) planes_collect(e, ns, st);
 		return;
 	}
@@ -1784,47 +1665,24 @@ void crack_pass(
 		trail_lds_used = lds;
 		HT_MARK("c:setup");
 
-		// The serial k_trail_walk keeps 1 wavefront per slice busy for ~1 ms while the chip idles.
-		// Slices can be processed in groups on their own streams (CKL_TRAIL_GROUPS): while one
-		// group is in its DFS the others run their parallel stages.
-		uint32_t groups = 1u;      // measured at C2: 2 groups between -0.17 and +0.1 ms from run to run, 4 and 8 slower (the DFS wavefronts want their SIMDs to themselves)
-		if (const char* env = getenv("CKL_TRAIL_GROUPS")) groups = static_cast<uint32_t>(std::max(1, atoi(env)));
-		groups = std::min<uint32_t>(std::min<uint32_t>(groups, ns), kTrailStreams);
-		const bool stagger = getenv("CKL_TRAIL_STAGGER") != nullptr;
-		if (groups > 1) CKL_HIP(hipEventRecord(e.ev_fork, s));
-		for (uint32_t g = 0; g < groups; g++) {
-			const uint32_t z0 = static_cast<uint32_t>(static_cast<uint64_t>(ns) * g / groups);
-			const uint32_t z1 = static_cast<uint32_t>(static_cast<uint64_t>(ns) * (g + 1) / groups);
-			const uint32_t gn = z1 - z0;
-			if (gn == 0) continue;
-			// group 0 stays on the session's own stream: the runtime multiplexes streams onto few hardware
-			// queues (4 by default), streams created later share one and serialise
-			if (g > 0 && !e.trail_stream[g - 1]) CKL_HIP(hipStreamCreateWithFlags(&e.trail_stream[g - 1], hipStreamNonBlocking));      // only when slice groups are asked for
-			hipStream_t gs = g == 0 ? s : e.trail_stream[g - 1];
-			// staggered: a group's chip-filling kernels start when the previous group's are through, i.e. beside
-			// that group's serial walk (one wavefront per slice), instead of all groups at once
-			if (g > 0) CKL_HIP(hipStreamWaitEvent(gs, stagger ? e.ev_pre[g - 1] : e.ev_fork, 0));
-			ta.z0 = z0;
-			fa.z0 = z0;
-			if (any) {
-				hipLaunchKernelGGL(k_trail_nodes, dim3(e.graph_blocks, gn), dim3(kBlock), 0, gs, ta);
-				hipLaunchKernelGGL(k_trail_segments, dim3(dart_blocks, gn), dim3(kBlock), 0, gs, ta);
-				if (max_cocap) hipLaunchKernelGGL(k_trail_loops, dim3((max_cocap + kBlock - 1) / kBlock, gn), dim3(kBlock), 0, gs, ta);
-				hipLaunchKernelGGL(k_trail_components, dim3(gn), dim3(kCompBlock), clds, gs, ta, static_cast<uint32_t>(clds));
-			}
-			if (g == 0) CKL_HIP(hipEventRecord(e.evd0, gs));
-			if (groups > 1) CKL_HIP(hipEventRecord(e.ev_pre[g], gs));
-			hipLaunchKernelGGL(k_trail_walk, dim3(gn), dim3(kWave), lds, gs, ta, static_cast<uint32_t>(lds));
-			if (g == 0) CKL_HIP(hipEventRecord(e.evd1, gs));
-			hipLaunchKernelGGL(k_trail_items, dim3(gn), dim3(kItemsBlock), 0, gs, ta);
-			hipLaunchKernelGGL(k_trail_offsets, dim3(gn), dim3(kBlock), 0, gs, ta);
-			hipLaunchKernelGGL(k_trail_expand, dim3((max_icap + kExpandChunk * kWaves - 1) / (kExpandChunk * kWaves), gn), dim3(kBlock), 0, gs, ta);
-			hipLaunchKernelGGL(k_finish, dim3(gn), dim3(kFinishBlock), 0, gs, fa);
-			if (g > 0) {
-				CKL_HIP(hipEventRecord(e.ev_join[g], gs));
-				CKL_HIP(hipStreamWaitEvent(s, e.ev_join[g], 0));
-			}
+		// (Slice groups on streams of their own, so that one group's parallel stages run beside another's serial
+		// k_trail_walk, measured at C2: 2 groups between -0.17 and +0.1 ms from run to run, 4 and 8 slower — the
+		// DFS wavefronts want their SIMDs to themselves.)
+		ta.z0 = 0;
+		fa.z0 = 0;
+		if (any) {
+			hipLaunchKernelGGL(k_trail_nodes, dim3(e.graph_blocks, ns), dim3(kBlock), 0, s, ta);
+			hipLaunchKernelGGL(k_trail_segments, dim3(dart_blocks, ns), dim3(kBlock), 0, s, ta);
+			if (max_cocap) hipLaunchKernelGGL(k_trail_loops, dim3((max_cocap + kBlock - 1) / kBlock, ns), dim3(kBlock), 0, s, ta);
+			hipLaunchKernelGGL(k_trail_components, dim3(ns), dim3(kCompBlock), clds, s, ta, static_cast<uint32_t>(clds));
 		}
+		CKL_HIP(hipEventRecord(e.evd0, s));
+		hipLaunchKernelGGL(k_trail_walk, dim3(ns), dim3(kWave), lds, s, ta, static_cast<uint32_t>(lds));
+		CKL_HIP(hipEventRecord(e.evd1, s));
+		hipLaunchKernelGGL(k_trail_items, dim3(ns), dim3(kItemsBlock), 0, s, ta);
+		hipLaunchKernelGGL(k_trail_offsets, dim3(ns), dim3(kBlock), 0, s, ta);
+		hipLaunchKernelGGL(k_trail_expand, dim3((max_icap + kExpandChunk * kWaves - 1) / (kExpandChunk * kWaves), ns), dim3(kBlock), 0, s, ta);
+		hipLaunchKernelGGL(k_finish, dim3(ns), dim3(kFinishBlock), 0, s, fa);
 	}
 	CKL_HIP(hipEventRecord(e.evk1, s));
 	HT_MARK("c:enqueue");
@@ -2439,13 +2297,11 @@ std::vector<uint8_t> pins_section_plain(
 	unsigned long long* choice = nullptr;
 	const uint64_t* first_any = nullptr;
 	PinVolume v;
-	if (getenv("CKL_PINS_ALONE")) CKL_HIP(hipStreamSynchronize(e.stream));      // measuring: the pin kernels without the trail's beside them
 	// The labels' first runs are final after the first column pass: their lists are made there and come to the host
 	// on a stream of their own, and the host builds the label table (7 ms at C4) while the later passes still run.
 	PinLabelLists lists;
-	const bool early_table = !getenv("CKL_PINS_LATE_TABLE");
 	pin_passes_device<LABEL>(e, labels, cc, sx, sy, sz, N, v, choice, first_any,
-		early_table ? std::function<void(const uint64_t*)>([&](const uint64_t* fa) { pin_label_table_enqueue(e, comp_label, fa, N, lists); }) : std::function<void(const uint64_t*)>());
+		[&](const uint64_t* fa) { pin_label_table_enqueue(e, comp_label, fa, N, lists); });
 	const uint32_t nb = static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock);
 	const uint32_t pieces = static_cast<uint32_t>((N + kPinScanPiece - 1) / kPinScanPiece);
 	DevBuf<uint32_t> d_zep, d_count, d_ze, d_ids;
@@ -2458,7 +2314,7 @@ std::vector<uint8_t> pins_section_plain(
 	hipLaunchKernelGGL(k_pin_scan_tops, dim3(1), dim3(kPinBlock), 0, s, d_piece.p, pieces);
 	hipLaunchKernelGGL(k_pin_scan_offsets, dim3(pieces), dim3(kPinBlock), 0, s, d_count.p, N, d_piece.p, pieces, d_off.p);
 	std::shared_ptr<const PinLabelTable> table;
-	if (early_table) {
+	{
 		PinCandidates lc;
 		pin_label_table_collect(e, lists, lc);
 		HT_MARK("p:lists");
@@ -2658,7 +2514,7 @@ void encode_typed(
 	bool labels_at_walk = false;
 	if (labels_first && !graph_done) flat_enqueue(e, sx, sy, sz);
 	const bool trail_cached = !graph_done && planes_cached && ov && ov->has_model && head.markov_model_order > 0 && e.trail_for == static_cast<const void*>(labels)
-		&& e.trail_perm == (head.crack_format == PERMISSIBLE) && e.trail_order == head.markov_model_order && !getenv("CKL_NO_TRAIL_REUSE");
+		&& e.trail_perm == (head.crack_format == PERMISSIBLE) && e.trail_order == head.markov_model_order;
 	e.trail_for = nullptr;
 	if (graph_done && e.graph_permissible != (head.crack_format == PERMISSIBLE)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: device and host disagree on the crack format");
 	if (!trail_cached && !graph_done) graph_pass(e, sx, sy, sz, head.crack_format == PERMISSIBLE ? 1 : 0);
@@ -2738,7 +2594,7 @@ void encode_typed(
 		else {
 			label_bytes = flat_section(e, N, stored_width, component_width, static_cast<uint32_t>(sz), ov);
 			HT_MARK("label_table");
-			labels_stay = e.async_host_copy && e.keep_device_stream && !e.defer_codes && label_bytes > 0 && !getenv("CKL_LABELS_CRC_HOST");
+			labels_stay = e.async_host_copy && e.keep_device_stream && !e.defer_codes && label_bytes > 0;
 			// The output buffer is taken now, sized with an estimate of the crack code bytes, so that
 			// the label section is copied out and checksummed while the trail still runs; a stream
 			// that outgrows the estimate is moved to a larger buffer at assembly.
@@ -2995,9 +2851,7 @@ int ckl_encoder_create(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int 
 			// the serial walk (k_trail_walk, one wavefront per slice) starts, whose step time suffers beside them
 			int lo = 0, hi = 0;
 			CKL_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-			const char* env = getenv("CKL_LABEL_STREAM_PRIORITY");
-			const int prio = env ? atoi(env) : hi;
-			CKL_HIP(hipStreamCreateWithPriority(&e->stream2, hipStreamNonBlocking, prio));
+			CKL_HIP(hipStreamCreateWithPriority(&e->stream2, hipStreamNonBlocking, hi));
 		}
 		CKL_HIP(hipEventCreate(&e->ev0));
 		CKL_HIP(hipEventCreate(&e->ev1));
@@ -3006,10 +2860,7 @@ int ckl_encoder_create(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int 
 		CKL_HIP(hipEventCreate(&e->evd0));
 		CKL_HIP(hipEventCreate(&e->evd1));
 		CKL_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-		CKL_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
 		CKL_HIP(hipEventCreateWithFlags(&e->ev_prezero, hipEventDisableTiming));
-		for (auto& ev : e->ev_join) CKL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-		for (auto& ev : e->ev_pre) CKL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 		*out = e.release();
 		return CKL_OK;
 	}

@@ -342,7 +342,7 @@ void host_parallel_for(size_t n, size_t grain, const std::function<void(size_t, 
 		catch (const std::exception& e) { errors[t] = e.what(); if (errors[t].empty()) errors[t] = "error"; }
 		catch (...) { errors[t] = "error"; }
 	};
-	if (getenv("CKL_PINS_NO_POOL") || !HostPool::get().run(want, job)) {
+	if (!HostPool::get().run(want, job)) {
 		std::vector<std::thread> pool;
 		for (size_t t = 0; t < want; t++) pool.emplace_back([&, t]() { job(t); });
 		for (auto& th : pool) th.join();

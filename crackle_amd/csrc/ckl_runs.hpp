@@ -295,11 +295,10 @@ static __global__ void __launch_bounds__(kBlock) k_run_union_seams(RunGeom g, Ru
 // LDS table of a strip: the smaller, the more workgroups share a CU (the kernel waits on
 // memory and LDS round trips, not on arithmetic); strips with more runs use the global forest
 static inline uint32_t run_strip_runs() {
-	if (const char* env = getenv("CKL_STRIP_RUNS")) { const int v = atoi(env); if (v >= 64 && v <= 16384) return static_cast<uint32_t>(v); }      // tuning aid
+	if (const char* env = getenv("CKL_STRIP_RUNS")) { const int v = atoi(env); if (v >= 64 && v <= 16384) return static_cast<uint32_t>(v); }      // testing: 64 forces the global forest
 	return kStripRuns;
 }
 static inline uint32_t run_strip_rows(uint32_t row_words) {
-	if (const char* env = getenv("CKL_STRIP_ROWS")) { const int v = atoi(env); if (v >= 2) return static_cast<uint32_t>(v); }      // tuning aid
 	const uint32_t r = 1024u / (row_words ? row_words : 1u);      // 32K pixels per strip: the LDS table covers one run per ~10 pixels
 	return r < 2u ? 2u : r;
 }

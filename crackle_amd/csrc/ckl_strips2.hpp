@@ -27,7 +27,6 @@ namespace dev {
 
 struct Strip2Args {
 	uint32_t rsh;       // log2(row_words)
-	uint32_t variant;   // tuning builds: bit 0 = edge-list unions as in k_strip_ccl (A/B)
 };
 
 // Half a record (positions 8 h .. 8 h + 7) into the strip's plane pieces: `lds` = piece of plane V (words 0 .. nw,
@@ -71,7 +70,7 @@ constexpr uint32_t kStrip2Words = kStripCclWords;
 // per-workgroup cycle stamps of the tuning build: [workgroup][kStrip2Stamps] raw s_memtime values
 constexpr uint32_t kStrip2Stamps = 8;
 
-template <bool DIAG, bool EDGELIST>
+template <bool DIAG>
 __device__ __forceinline__ void strip_ccl2_body(
 	const RunGeom& g, const StripArrays& sa, const RecordLists& rl, const uint32_t* __restrict__ G, uint32_t n_pixels, uint32_t rsh,
 	unsigned long long* __restrict__ diag, uint32_t zi, uint32_t k, uint32_t* lds
@@ -200,44 +199,15 @@ __device__ __forceinline__ void strip_ccl2_body(
 			const uint32_t prev = j ? up[j - 1] : upl0;
 			c[j] = up[j] & (~((up[j] << 1) | (prev >> 31)) | b[j] | b_up[j]);
 		}
-		if constexpr (EDGELIST) {
-			const uint32_t n_e = __popc(c[0]) + __popc(c[1]) + __popc(c[2]) + __popc(c[3]);
-			uint32_t ve[1] = { n_e }, te[1];
-			block_excl_add<1>(ve, te, s_scan);      // its barriers: every read of s_b / s_pool is done
-			const uint32_t n_edges = te[0];
-			if (n_edges <= kStripEdgeCap) {      // uniform
-				uint32_t at = ve[0];
+		// a run's first contact with the row above becomes its parent: one atomicMin (the run above has the
+		// smaller index); a contact that finds another link in place unites the two runs above
 #pragma unroll
-				for (uint32_t j = 0; j < 4; j++) {
-					for (uint32_t cc = c[j]; cc; cc &= cc - 1u) {
-						const uint32_t m = cc ^ (cc - 1u);
-						s_mem[at++] = (l[j] + __popc(b[j] & m) - 1u) | ((l_up[j] + __popc(b_up[j] & m) - 1u) << 16);
-					}
-				}
-				__syncthreads();
-				for (uint32_t e = t; e < n_edges; e += kBlock) { const uint32_t pr = s_mem[e]; sm_unite(s_par, pr & 0xFFFFu, pr >> 16); }
-			}
-			else {
-#pragma unroll
-				for (uint32_t j = 0; j < 4; j++) {
-					for (uint32_t cc = c[j]; cc; cc &= cc - 1u) {
-						const uint32_t m = cc ^ (cc - 1u);
-						sm_unite(s_par, l[j] + __popc(b[j] & m) - 1u, l_up[j] + __popc(b_up[j] & m) - 1u);
-					}
-				}
-			}
-		}
-		else {
-			// a run's first contact with the row above becomes its parent: one atomicMin (the run above has the
-			// smaller index); a contact that finds another link in place unites the two runs above
-#pragma unroll
-			for (uint32_t j = 0; j < 4; j++) {
-				for (uint32_t cc = c[j]; cc; cc &= cc - 1u) {
-					const uint32_t m = cc ^ (cc - 1u);
-					const uint32_t jh = l[j] + __popc(b[j] & m) - 1u, ju = l_up[j] + __popc(b_up[j] & m) - 1u;
-					const uint32_t old = atomicMin(s_par + jh, ju);
-					if (old != jh && old != ju) sm_unite(s_par, ju, old);
-				}
+		for (uint32_t j = 0; j < 4; j++) {
+			for (uint32_t cc = c[j]; cc; cc &= cc - 1u) {
+				const uint32_t m = cc ^ (cc - 1u);
+				const uint32_t jh = l[j] + __popc(b[j] & m) - 1u, ju = l_up[j] + __popc(b_up[j] & m) - 1u;
+				const uint32_t old = atomicMin(s_par + jh, ju);
+				if (old != jh && old != ju) sm_unite(s_par, ju, old);
 			}
 		}
 	}
@@ -324,13 +294,10 @@ __device__ __forceinline__ void strip_ccl2_body(
 	stamp(6);
 }
 
-template <bool DIAG, bool EDGELIST>
+template <bool DIAG>
 static __global__ void __launch_bounds__(kBlock, 7) k_strip_ccl2(RunGeom g, StripArrays sa, RecordLists rl, const uint32_t* __restrict__ G, uint32_t n_pixels, Strip2Args a2, unsigned long long* __restrict__ diag) {
 	__shared__ __attribute__((aligned(16))) uint32_t s_lds[kStrip2Words];
-	uint32_t zl, k;
-	if (sa.layout & 4u) strip_of_block(sa, zl, k);
-	else { zl = blockIdx.y; k = blockIdx.x; }
-	strip_ccl2_body<DIAG, EDGELIST>(g, sa, rl, G, n_pixels, a2.rsh, diag, zl + sa.zbase, k, s_lds);
+	strip_ccl2_body<DIAG>(g, sa, rl, G, n_pixels, a2.rsh, diag, blockIdx.y + sa.zbase, blockIdx.x, s_lds);
 }
 
 }  // namespace dev

@@ -74,7 +74,7 @@ struct TrailArgs {
 	uint32_t sx, sy, inv;
 	uint32_t sxe, sye;
 	uint32_t nverts;
-	uint32_t z0;                 // first slice of this launch (the trail runs in slice groups on several streams)
+	uint32_t z0;                 // first slice of this launch
 	const uint32_t* max_steps;   // [nslices] crack edges of the slice + 1
 	uint32_t graph_blocks;       // workgroups per slice of k_trail_graph / k_trail_nodes
 	const uint32_t* blk_special; // [nslices][graph_blocks] exclusive prefix of the node counts

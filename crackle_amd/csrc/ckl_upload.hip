@@ -6,7 +6,6 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <cstdlib>
 
 namespace ckl {
 
@@ -24,7 +23,7 @@ __global__ void __launch_bounds__(256) k_upload_small(const uint8_t* __restrict_
 
 void upload_small(void* dst_device, const void* src_host, size_t bytes, hipStream_t s, const void* block) {
 	if (bytes == 0) return;
-	if (block && host_out_is_pinned(block) && !getenv("CKL_UPLOAD_MEMCPY")) {
+	if (block && host_out_is_pinned(block)) {
 		hipLaunchKernelGGL(k_upload_small, dim3(static_cast<uint32_t>((bytes + 4095) / 4096)), dim3(256), 0, s,
 			static_cast<const uint8_t*>(src_host), static_cast<uint8_t*>(dst_device), bytes);
 		return;

@@ -51,36 +51,33 @@ def test_baseline_configurations_stay_on_the_fast_kernels(name, shape, dt, opts,
   assert torch.equal(out, vol), name
 
 
-def test_fused_strip_kernel_is_bit_exact(monkeypatch):
-  """k_strip_fused (opt-in: strips, resolve and paint in one ticketed launch) against the
-  input, for 4- and 8-byte labels and a shape with ragged rows."""
-  monkeypatch.setenv("CKL_DECODE_FUSED", "1")
+# k_strip_ccl (ckl_strips.hpp) takes rows that are not a power of two of 4 .. 512 plane words
+STRIP_V1 = ["k_crack_match", "k_strip_ccl", "k_slice_resolve", "k_paint_strips"]
+# shape, dtype, offset added to the labels, voronoi cell, kernels that decode it
+SMALL_CASES = [
+  ((1024, 1024, 24), np.uint32, 0, (32, 32, 8), FAST_FLAT),
+  ((1024, 1024, 9), np.uint64, 1 << 40, (32, 32, 8), FAST_FLAT),
+  ((320, 288, 5), np.uint16, 0, (16, 16, 4), STRIP_V1),
+  ((36, 300, 3), np.uint8, 0, (8, 8, 4), STRIP_V1),
+]
+
+
+@pytest.mark.parametrize("shape,dt,offset,cell,stages", SMALL_CASES, ids=["1024x1024x24-u32", "1024x1024x9-u64", "320x288x5-u16", "36x300x3-u8"])
+def test_label_widths_and_ragged_rows_stay_on_the_strip_kernels(shape, dt, offset, cell, stages):
+  """4- and 8-byte labels, and 1- and 2-byte labels on rows of 10 and 2 plane words, round trip on the strip path."""
   dev = torch.device("cuda:0")
-  cases = [((1024, 1024, 24), np.uint32, 0, (32, 32, 8)), ((1024, 1024, 9), np.uint64, 1 << 40, (32, 32, 8)),
-           ((320, 288, 5), np.uint16, 0, (16, 16, 4)), ((36, 300, 3), np.uint8, 0, (8, 8, 4))]
-  for shape, dt, offset, cell in cases:
-    vol = synth.voronoi_labels(shape, dt, seed=7, device=dev, offset=offset, cell=cell)
-    be = ckd.HipBackend(0)
-    codec = ckd.ShardedCodec(be, device=dev)
-    binary = codec.compress(vol, shape)
-    out = torch.empty_like(vol)
-    sess = codec.open_decoder(binary, shape)
-    sess.run(out)
-    names = [n for n, _ in sess.stages()]
-    sess.close()
-    assert names == ["k_crack_match", "k_strip_fused"], names
-    assert torch.equal(out, vol), (shape, dt)
-  # a slice with more strip components than the resolver's LDS table holds: the session hands over to the three launches
-  vol = synth.voronoi_labels((1024, 1024, 4), np.uint32, seed=8, device=dev, cell=(12, 12, 4))
+  vol = synth.voronoi_labels(shape, dt, seed=7, device=dev, offset=offset, cell=cell)
   be = ckd.HipBackend(0)
   codec = ckd.ShardedCodec(be, device=dev)
-  binary = codec.compress(vol, (1024, 1024, 4))
+  binary = codec.compress(vol, shape)
   out = torch.empty_like(vol)
-  sess = codec.open_decoder(binary, (1024, 1024, 4))
-  sess.run(out)
-  assert "k_strip_fused" not in [n for n, _ in sess.stages()]
+  sess = codec.open_decoder(binary, shape)
+  for _ in range(2):
+    sess.run(out)
+    names = [n for n, _ in sess.stages()]
+    assert names == stages, f"{shape} {np.dtype(dt).name}: decoded by {names}"
   sess.close()
-  assert torch.equal(out, vol)
+  assert torch.equal(out, vol), (shape, dt)
 
 
 def test_stage_events_can_be_switched_off():

@@ -1,7 +1,6 @@
 """Per-stage / per-phase timing of the C2 workload (device resident), for kernel work.
   python tools/stage_diag.py [SX SY SZ] [--markov N]
-Env: CKL_DECODE_DIAG=1 adds the phase cycle counters of k_decode_cracks,
-     CKL_WALK_DIAG=1 those of the encoder's walk kernel."""
+Env: CKL_DECODE_DIAG=1 adds the phase cycle counters of k_decode_cracks."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,13 +22,9 @@ for it in range(3):
   torch.cuda.synchronize(); t1 = time.perf_counter()
   s = codec.open_decoder(b, (sx, sy, sz))
   torch.cuda.synchronize(); t2 = time.perf_counter()
-  try:
-    s.run(out)
-  except RuntimeError as exc:
-    if not os.environ.get("CKL_ABLATE_NOCHECK"):
-      raise
+  s.run(out)
   torch.cuda.synchronize(); t3 = time.perf_counter()
   print(f"iter {it}: encode {1e3*(t1-t0):.2f} ms  decode {1e3*(t3-t2):.2f} ms  (device pipeline {s.timing()[0]:.2f} ms)  bytes {len(b)}")
   print("   stages: " + "  ".join(f"{n}={ms:.3f}" for n, ms in s.stages()))
   s.close()
-assert os.environ.get("CKL_ABLATE_NOCHECK") or torch.equal(out, vol)
+assert torch.equal(out, vol)

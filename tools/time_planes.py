@@ -1,4 +1,4 @@
-"""Wall time of the label-plane pass alone (ckl_encoder_stats: k_label_planes_fast + k_planes_reduce + one report back)."""
+"""Wall time of the label-plane pass alone (ckl_encoder_stats: k_label_planes_stream + k_planes_reduce + one report back)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

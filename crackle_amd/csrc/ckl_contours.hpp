@@ -187,7 +187,6 @@ __global__ void __launch_bounds__(64) k_trace_contours(ContourArgs a) {
 		if (m_start == 0u) {
 			// an isolated pixel (dual_graph.hpp:168-171)
 			if (lane == 0) { vis[node >> 5] |= 1u << (node & 31u); if (room) out[0] = node; }
-			if (!room) flags |= kContourRawOverflow;
 			n = 1;
 		}
 		else {
@@ -201,15 +200,15 @@ __global__ void __launch_bounds__(64) k_trace_contours(ContourArgs a) {
 			// so the loop stays on the scalar unit.
 			uint32_t seen = 0, bad = 0;
 			if (lane == 0) {
-				if (room) out[0] = start; else bad = kContourRawOverflow;
+				if (room) out[0] = start;
 				if (wall_r && walked_r) __hip_atomic_fetch_or(walked_r + (start >> 5), 1u << (start & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				n = 1;
 				uint32_t next = ending;
 				do {
 					node += delta(next);
-					if (node >= sxy || n >= room) { bad = node >= sxy ? kContourOpenWalk : kContourRawOverflow; break; }
+					if (node >= sxy) { bad = kContourOpenWalk; break; }
 					const uint32_t m = dir_of(node);      // issued before the visited bit is touched: the two latencies overlap
-					out[n] = node;
+					if (n < room) out[n] = node;      // past the room the walk goes on unstored: only a kept contour overflows
 					if (node < mn) { mn = node; mn_pos = n; }
 					n++;
 					// nothing on the walk depends on the old bit: swapped in and counted
@@ -234,6 +233,7 @@ __global__ void __launch_bounds__(64) k_trace_contours(ContourArgs a) {
 		pos = start + 1u;
 		if (flags) break;
 		if (n == 0u || n == already) continue;      // nothing new on this loop (dual_graph.hpp:199-201)
+		if (n > room) { flags |= kContourRawOverflow; break; }
 		if (n_contours < a.tab_cap) { if (lane == 0) table[n_contours] = make_uint4(tail, n, mn_pos, mn); }
 		else { flags |= kContourTableOverflow; break; }
 		n_contours++;

@@ -3545,7 +3545,16 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 	const uint32_t ns = d.nslices;
 	out.offsets.assign(1, 0);
 	if (d.sxy == 0 || ns == 0) return;
-	if (d.sxy >= 0xFFFFFFF0ull / 4) throw Error(CKL_ERR_ARG, "crackle_amd: point_cloud: slices of this size are not supported");
+	// The most contour nodes the tracer keeps for one slice.  A walk is one orbit of the wall
+	// follower on the darts (directed edges) of the 4-connected pixel graph: it never passes a dart
+	// twice and stores one node per step plus its start.  The walks in either sense of one loop
+	// pass the same pixels, so a loop is kept at most once (dual_graph.hpp:199-201), and every dart
+	// lies on one loop: the kept walks store at most 2 E nodes, E = 2 sx sy - sx - sy edges, plus
+	// one start per kept contour, at most one per pixel (each passes a pixel not passed before).
+	// Dropped walks store nothing past the buffer (k_trace_contours).  raw and the kernel's tail
+	// and room are 32-bit: larger slices are refused.
+	const uint64_t raw_worst = 2 * (2 * d.sxy - h.sx - h.sy) + d.sxy;
+	if (raw_worst > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: point_cloud: slices of 2^32 contour nodes or more (5 sx sy - 2 sx - 2 sy) are not supported");
 	{
 		std::vector<uint32_t> errs(ns);
 		decoder_run(d, nullptr, 0, 0, 0, nullptr, false, errs.data());
@@ -3622,7 +3631,7 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 	struct Chunk { uint32_t z0, n; uint32_t raw_cap; std::unique_ptr<DevBuf<uint32_t>> raw; };
 	std::vector<Chunk> chunks;
 	const uint64_t budget = 3ull << 30;
-	uint32_t raw_cap0 = static_cast<uint32_t>(std::min<uint64_t>(d.sxy / 2 + 4096, 8ull * d.sxy + 16));
+	uint32_t raw_cap0 = static_cast<uint32_t>(std::min<uint64_t>(d.sxy / 2 + 4096, raw_worst));
 	uint32_t tab_cap0 = static_cast<uint32_t>(std::min<uint64_t>(d.sxy / 32 + 1024, d.sxy + 1));
 	if (const char* env = getenv("CKL_CONTOUR_SMALL")) { raw_cap0 = std::max(16, atoi(env)); tab_cap0 = std::max(2, atoi(env) / 8); }      // testing: forces the second pass
 	DevBuf<uint8_t> d_dirs;
@@ -3678,7 +3687,7 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 			if (flags & kContourOpenWalk) throw Error(CKL_ERR_RUNTIME, "crackle_amd: point_cloud: a contour walk did not close");
 			if (flags) {
 				if (attempt) throw Error(CKL_ERR_RUNTIME, "crackle_amd: point_cloud: contour buffers overflow");
-				raw_cap = static_cast<uint32_t>(8ull * d.sxy + 16);
+				raw_cap = static_cast<uint32_t>(std::max<uint64_t>(raw_worst, 1));
 				tab_cap = sxy + 1;
 				continue;
 			}

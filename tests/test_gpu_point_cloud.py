@@ -116,8 +116,9 @@ def test_point_cloud_signed_labels(checker):
 
 
 def test_point_cloud_paths(checker, monkeypatch):
-  """The visited bits in HBM (slices of more than ~1.2 M pixels use it), the second pass with
-  worst-case buffers after an overflow, several z-chunks."""
+  """The visited bits in HBM (slices of more than ~1.2 M pixels use it) and the second pass with
+  worst-case buffers after an overflow, both through switches; every volume here is one z-chunk
+  (natural shapes on both sides of each: tests/test_gpu_consumer_edges.py)."""
   arr = VOLUMES["rings"]()
   binary = checker.compress(arr)
   want = checker.point_cloud(binary, 0, -1, None, False)

@@ -179,7 +179,7 @@ def roundtrip(binary, arr, monkeypatch, window=None, labels=(), env=None, what="
 
 
 def _np_stats(arr):
-  """{label: (count, centroid, box)} from numpy."""
+  """{label: (count, centroid, box)} from numpy: centroids are exact int64 coordinate sums divided once in float64."""
   sx, sy, sz = arr.shape
   flat = arr.reshape(-1, order="F")
   u, inv = np.unique(flat, return_inverse=True)
@@ -189,11 +189,11 @@ def _np_stats(arr):
   order = np.argsort(inv, kind="stable")
   starts = np.concatenate([[0], np.cumsum(cnt)[:-1]])
   out = {}
-  sums = [np.bincount(inv, weights=c.astype(np.float64)) for c in (x, y, z)]
+  sums = [np.add.reduceat(c[order], starts) for c in (x, y, z)]      # exact: int64
   mins = [np.minimum.reduceat(c[order], starts) for c in (x, y, z)]
   maxs = [np.maximum.reduceat(c[order], starts) for c in (x, y, z)]
   for i, lab in enumerate(u.tolist()):
-    out[int(lab)] = (int(cnt[i]), np.array([s[i] for s in sums]) / float(cnt[i]),
+    out[int(lab)] = (int(cnt[i]), np.array([np.float64(s[i]) / np.float64(cnt[i]) for s in sums]),
                      [int(m[i]) for m in mins] + [int(m[i]) for m in maxs])
   return out
 
@@ -205,7 +205,7 @@ def check_consumers(binary, arr, vcg=False):
   cents = crackle_amd.centroids(binary)
   assert sorted(cents) == sorted(want)
   for k, (_, c, _) in want.items():
-    assert np.allclose(cents[k], c, rtol=1e-12, atol=0), k
+    assert cents[k].dtype == np.float64 and np.array_equal(cents[k], c), (k, cents[k], c)
   boxes = crackle_amd.bounding_boxes(binary, no_slice_conversion=True)
   assert {k: [int(v) for v in b] for k, b in boxes.items()} == {k: v[2] for k, v in want.items()}
   if vcg:

@@ -30,6 +30,8 @@
 //   k_paint_runs      streams the output: per 4 pixels one plane word, a popcount and a
 //                     look-up in an LDS-staged run->label table; 16-byte streaming stores.
 //   k_run_stats       per-label voxel counts, coordinate sums and boxes from the runs
+//   k_run_contacts    faces between touching labels per axis from the runs (contacts)
+//   k_contacts_compact  the occupied entries of its pair table, packed
 //   k_vcg             voxel connectivity graph from the planes (+ labels for the z bits)
 #include "ckl_common.hpp"
 #include "ckl_runs.hpp"
@@ -1541,6 +1543,206 @@ static __global__ void k_stats_init(uint32_t* box, uint32_t n_table) {
 	if (i >= n_table) return;
 	box[6ull * i + 0] = box[6ull * i + 1] = box[6ull * i + 2] = 0xFFFFFFFFu;
 	box[6ull * i + 3] = box[6ull * i + 4] = box[6ull * i + 5] = 0;
+}
+
+// ------------------------------------------------------------------------------
+// contacts (operations.hpp:850-1021): faces between touching labels, counted per axis from the
+// runs.  The reference walks every pixel of two consecutive component images and adds a float
+// per face into a hash map.  Here a thread takes one run of a slice and counts
+//   x  the boundary to the next run of its row, when the two components differ (one face);
+//   y  the overlaps with the runs of the row above in the same slice whose component differs;
+//   z  the overlaps with the runs of the same row in the previous slice of the range whose label
+//      differs (only for z > z_start, as the reference).
+// The run of the other row that holds the run's first pixel is found in O(1) through word_base
+// and the vertical-crack plane (as k_label_map_pins does); the following runs of that row are
+// walked until the run's last pixel.  Labels are indices into the sorted label table
+// (k_component_label_index), a pair is the 64-bit key (min << 32 | max).  Exact integer counts:
+// per workgroup in an LDS open-addressing table, flushed into a global one with 64-bit counters.
+// A key that finds no room in the LDS table goes to the global table directly; a global table
+// that fills sets a flag and the host runs the pass again with twice the capacity.
+// ------------------------------------------------------------------------------
+constexpr int kContactBlock = 256;
+constexpr uint32_t kContactPer = 8;                                 // runs per thread
+constexpr uint32_t kContactRuns = kContactBlock * kContactPer;      // runs per workgroup
+constexpr uint32_t kContactLds = 1024;                              // LDS table entries (power of two)
+constexpr uint32_t kContactProbes = 32;                             // LDS probes before a key goes to the global table
+constexpr uint32_t kContactGlobalProbes = 128;                      // global probes before the table counts as full
+constexpr unsigned long long kContactEmpty = ~0ull;                 // never a key: table indices are below 2^32 - 1
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;
+enum : uint32_t { CONTACT_FULL = 0, CONTACT_BADKEY = 1, CONTACT_COUNT = 2, CONTACT_FLAGS = 3 };
+
+struct ContactArgs {
+	const uint32_t* comp_key;        // [total_comp] label table index of every component (kNoKey: not in the table)
+	uint32_t zero_key;               // table index of label 0 (kNoKey: absent); its faces are dropped
+	uint32_t sx, n_pixels;
+	unsigned long long* keys;        // [cap] global table: pair keys, kContactEmpty where free
+	unsigned long long* counts;      // [cap][3] faces along x, y, z
+	uint32_t cap_mask;               // cap - 1, cap a power of two
+	uint32_t* flags;                 // [CONTACT_FLAGS]: full, a label outside the table, compacted entries
+};
+
+__device__ __forceinline__ uint32_t contact_hash(unsigned long long k) {
+	k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+	k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+	k ^= k >> 33;
+	return static_cast<uint32_t>(k);
+}
+
+// The table is full for a key that finds neither itself nor a free entry in kContactGlobalProbes
+// entries from its hash; a full table gives up at once (the pass runs again, twice as large).  No
+// count of the entries taken: one word that every new key adds to serialises the kernel.
+__device__ void contact_global(const ContactArgs& ca, unsigned long long key, uint32_t nx, uint32_t ny, uint32_t nz) {
+	if (__hip_atomic_load(ca.flags + CONTACT_FULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+	const uint32_t h = contact_hash(key);
+	for (uint32_t p = 0; p < kContactGlobalProbes && p <= ca.cap_mask; p++) {
+		const uint32_t slot = (h + p) & ca.cap_mask;
+		unsigned long long cur = ca.keys[slot];      // a slot changes once, from empty to its key: a stale read is settled by the CAS
+		if (cur == kContactEmpty) {
+			cur = atomicCAS(ca.keys + slot, kContactEmpty, key);
+			if (cur == kContactEmpty) cur = key;
+		}
+		if (cur == key) {
+			unsigned long long* c = ca.counts + 3ull * slot;
+			if (nx) atomicAdd(c + 0, static_cast<unsigned long long>(nx));
+			if (ny) atomicAdd(c + 1, static_cast<unsigned long long>(ny));
+			if (nz) atomicAdd(c + 2, static_cast<unsigned long long>(nz));
+			return;
+		}
+	}
+	atomicOr(ca.flags + CONTACT_FULL, 1u);
+}
+
+// n faces along `axis` between the labels of table indices ka and kb
+__device__ __forceinline__ void contact_add(
+	const ContactArgs& ca, unsigned long long* s_key, uint32_t* s_cnt, uint32_t ka, uint32_t kb, uint32_t axis, uint32_t n
+) {
+	if (ka == ca.zero_key || kb == ca.zero_key) return;
+	const unsigned long long key = ka <= kb ? (static_cast<unsigned long long>(ka) << 32 | kb) : (static_cast<unsigned long long>(kb) << 32 | ka);
+	const uint32_t h = contact_hash(key);
+	for (uint32_t p = 0; p < kContactProbes; p++) {
+		const uint32_t slot = (h + p) & (kContactLds - 1);
+		unsigned long long cur = s_key[slot];
+		if (cur == kContactEmpty) {
+			cur = atomicCAS(s_key + slot, kContactEmpty, key);
+			if (cur == kContactEmpty) cur = key;
+		}
+		if (cur == key) { atomicAdd(s_cnt + 3 * slot + axis, n); return; }
+	}
+	contact_global(ca, key, axis == 0 ? n : 0u, axis == 1 ? n : 0u, axis == 2 ? n : 0u);
+}
+
+// faces between pixels [x0, x1] of a run (component cc, label index ka) and the runs of row y of
+// slice zj: by component (y faces, same slice) or by label (z faces, previous slice)
+__device__ __forceinline__ void contact_row(
+	const RunGeom& g, const RunArrays& r, const ContactArgs& ca, unsigned long long* s_key, uint32_t* s_cnt,
+	uint32_t zj, const uint32_t* key_j, uint32_t nce_j, uint32_t y, uint32_t x0, uint32_t x1, uint32_t cc, uint32_t ka, bool by_comp, uint32_t axis
+) {
+	const uint64_t rb = r.rbase[zj];
+	const uint32_t nj = r.nruns[zj];
+	const uint32_t row = y * ca.sx;
+	const uint32_t w = x0 >> 5;
+	uint32_t j = r.word_base[zj * g.plane_words + y * g.row_words + w] + __popc(g.breaks(zj, y, w) & mask_le(x0 & 31u)) - 1u;
+	if (j >= nj) { atomicOr(ca.flags + CONTACT_BADKEY, 1u); return; }
+	uint32_t s = r.run_start[rb + j] - row;
+	for (;;) {
+		// the run after the last one of a row starts the next row (or the slice ends): e <= sx
+		const uint32_t e = (j + 1 < nj ? r.run_start[rb + j + 1] : ca.n_pixels) - row;
+		const uint32_t ccj = r.run_cc[rb + j];
+		if (!by_comp || ccj != cc) {
+			const uint32_t kj = ccj < nce_j ? key_j[ccj] : kNoKey;
+			if (kj == kNoKey) atomicOr(ca.flags + CONTACT_BADKEY, 1u);
+			else if (by_comp || kj != ka) contact_add(ca, s_key, s_cnt, ka, kj, axis, min(e, x1 + 1) - max(s, x0));
+		}
+		if (e > x1) return;
+		j++;
+		s = e;
+	}
+}
+
+// grid = (ceil(most runs of a slice / kContactRuns), nslices), block = kContactBlock
+static __global__ void __launch_bounds__(kContactBlock) k_run_contacts(
+	RunGeom g, RunArrays r, const uint64_t* __restrict__ comp_off, const uint32_t* __restrict__ ncomp_expect, ContactArgs ca
+) {
+	__shared__ unsigned long long s_key[kContactLds];
+	__shared__ uint32_t s_cnt[3 * kContactLds];
+	__shared__ uint32_t s_stop;
+	const uint32_t zi = blockIdx.y;
+	const uint32_t n = r.nruns[zi];
+	const uint32_t i0 = blockIdx.x * kContactRuns;
+	if (i0 >= n) return;
+	if (threadIdx.x == 0) s_stop = __hip_atomic_load(ca.flags + CONTACT_FULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	for (uint32_t k = threadIdx.x; k < kContactLds; k += kContactBlock) {
+		s_key[k] = kContactEmpty;
+		s_cnt[3 * k] = 0; s_cnt[3 * k + 1] = 0; s_cnt[3 * k + 2] = 0;
+	}
+	__syncthreads();
+	if (s_stop) return;      // this pass runs again with a larger table: nothing it adds is kept
+	const uint64_t rb = r.rbase[zi];
+	const uint32_t nce = ncomp_expect[zi];
+	const uint32_t* key_z = ca.comp_key + comp_off[zi];
+	const uint32_t nce_p = zi ? ncomp_expect[zi - 1] : 0u;
+	const uint32_t* key_p = zi ? ca.comp_key + comp_off[zi - 1] : nullptr;
+	for (uint32_t k = 0; k < kContactPer; k++) {
+		const uint32_t i = i0 + k * kContactBlock + threadIdx.x;
+		if (i >= n) break;
+		const uint32_t a = r.run_start[rb + i];
+		const uint32_t b = i + 1 < n ? r.run_start[rb + i + 1] : ca.n_pixels;
+		const uint32_t cc = r.run_cc[rb + i];
+		const uint32_t y = a / ca.sx;
+		const uint32_t row = y * ca.sx;
+		const uint32_t x0 = a - row, x1 = b - 1 - row;
+		const uint32_t ka = cc < nce ? key_z[cc] : kNoKey;
+		if (ka == kNoKey) { atomicOr(ca.flags + CONTACT_BADKEY, 1u); continue; }
+		if (b < row + ca.sx) {      // the next run is in the same row
+			const uint32_t cc2 = r.run_cc[rb + i + 1];
+			if (cc2 != cc) {
+				const uint32_t kb = cc2 < nce ? key_z[cc2] : kNoKey;
+				if (kb == kNoKey) atomicOr(ca.flags + CONTACT_BADKEY, 1u);
+				else contact_add(ca, s_key, s_cnt, ka, kb, 0, 1);
+			}
+		}
+		if (y > 0) contact_row(g, r, ca, s_key, s_cnt, zi, key_z, nce, y - 1, x0, x1, cc, ka, true, 1);
+		if (zi > 0) contact_row(g, r, ca, s_key, s_cnt, zi - 1, key_p, nce_p, y, x0, x1, cc, ka, false, 2);
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < kContactLds; k += kContactBlock) {
+		const unsigned long long key = s_key[k];
+		if (key != kContactEmpty) contact_global(ca, key, s_cnt[3 * k], s_cnt[3 * k + 1], s_cnt[3 * k + 2]);
+	}
+}
+
+// the occupied entries of the global table, packed (in no particular order: the host sorts them);
+// one output offset per workgroup of kContactCompact entries
+constexpr uint32_t kContactCompactPer = 8;
+constexpr uint32_t kContactCompact = kBlock * kContactCompactPer;
+static __global__ void __launch_bounds__(kBlock) k_contacts_compact(
+	const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ counts, uint32_t cap,
+	unsigned long long* __restrict__ out_keys, unsigned long long* __restrict__ out_counts, uint32_t* flags
+) {
+	__shared__ uint32_t s_scan[kWaves];
+	__shared__ uint32_t s_base;
+	const uint32_t i0 = blockIdx.x * kContactCompact + threadIdx.x * kContactCompactPer;
+	unsigned long long k[kContactCompactPer];
+	uint32_t v[1] = { 0 }, total[1];
+#pragma unroll
+	for (uint32_t j = 0; j < kContactCompactPer; j++) {
+		k[j] = i0 + j < cap ? keys[i0 + j] : kContactEmpty;
+		v[0] += k[j] != kContactEmpty;
+	}
+	block_excl_add<1>(v, total, s_scan);
+	if (threadIdx.x == 0) s_base = total[0] ? atomicAdd(flags + CONTACT_COUNT, total[0]) : 0u;
+	__syncthreads();
+	uint32_t at = s_base + v[0];
+#pragma unroll
+	for (uint32_t j = 0; j < kContactCompactPer; j++) {
+		if (k[j] == kContactEmpty) continue;
+		const uint64_t i = i0 + j;
+		out_keys[at] = k[j];
+		out_counts[3ull * at] = counts[3 * i];
+		out_counts[3ull * at + 1] = counts[3 * i + 1];
+		out_counts[3ull * at + 2] = counts[3 * i + 2];
+		at++;
+	}
 }
 
 // ------------------------------------------------------------------------------
@@ -3527,6 +3729,119 @@ void decoder_vcg(ckl_decoder& d, uint8_t* out_device, uint64_t capacity, int con
 	CKL_HIP(hipGetLastError());
 }
 
+// the pipeline up to the run tables and the component -> label map (the integrity check's mode);
+// a slice that fails its checks raises as decoder_run does
+void decoder_run_tables(ckl_decoder& d) {
+	const uint32_t ns = d.nslices;
+	std::vector<uint32_t> errs(ns);
+	decoder_run(d, nullptr, 0, 0, 0, nullptr, false, errs.data());
+	for (uint32_t zi = 0; zi < ns; zi++) {
+		if (!errs[zi]) continue;
+		const std::string z = std::to_string(d.z_start + zi);
+		if (errs[zi] & (ERR_BOC | ERR_RANGE | ERR_CAPACITY)) throw Error(CKL_ERR_RUNTIME, "crackle: crack code is malformed or corrupted on z=" + z);
+		if (errs[zi] & ERR_NCOMP) throw Error(CKL_ERR_RUNTIME, "crackle: component count does not match the label section on z=" + z);
+		throw Error(CKL_ERR_CRC, "crackle: crack code crc mismatch on z=" + z);
+	}
+}
+
+// operations::contacts (src/operations.hpp:850-1021) over the decoder's range: the pairs of touching
+// labels (table values, a <= b as unsigned, ascending) and their faces along x, y, z.  One pipeline
+// run up to the run tables, then k_run_contacts and k_contacts_compact; a global table that fills
+// is cleared and the pass runs again with twice the capacity.
+void decoder_contacts(ckl_decoder& d, std::vector<uint64_t>& pairs, std::vector<uint64_t>& faces) {
+	const Header& h = d.head;
+	hipStream_t s = d.stream;
+	const uint32_t ns = d.nslices;
+	pairs.clear(); faces.clear();
+	if (d.sxy == 0 || ns == 0) return;
+	decoder_run_tables(d);
+	ensure_label_table(d);
+	const uint32_t n_table = static_cast<uint32_t>(d.stats_table.size());
+	if (d.total_comp == 0 || n_table == 0) return;
+	DevBuf<uint32_t> d_comp_key;
+	d_comp_key.ensure(d.total_comp);
+	hipLaunchKernelGGL(k_component_label_index, dim3(static_cast<uint32_t>((d.total_comp + 255) / 256)), dim3(256), 0, s,
+		d.d_label_map.p, d.total_comp, d.d_stats_table.p, n_table, d_comp_key.p);
+	std::vector<uint32_t> nruns(ns);
+	CKL_HIP(hipMemcpyAsync(nruns.data(), d.d_nruns.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	const uint32_t max_runs = *std::max_element(nruns.begin(), nruns.end());
+	if (max_runs == 0) return;
+
+	RunGeom g;
+	g.planeV = d.d_planes.p; g.planeH = d.d_planes.p + d.plane_words * ns;
+	g.row_words = d.row_words; g.plane_words = d.plane_words;
+	g.flip = (h.crack_format == IMPERMISSIBLE) ? 1u : 0u;
+	g.sx = h.sx; g.sy = h.sy;
+	RunArrays ra;
+	ra.word_base = d.d_word_base.p; ra.rbase = d.d_rbase.p; ra.rcap = d.d_rcap.p;
+	ra.parent = d.d_parent.p; ra.run_start = d.d_run_start.p; ra.run_cc = d.d_run_cc.p;
+	ra.nruns = d.d_nruns.p; ra.ncomp = d.d_ncomp.p; ra.slice_err = d.d_slice_err.p;
+
+	// First capacity: a label touches some 15 others in a segmentation of compact 3D cells
+	// (about 8 pairs per label), twice that as a margin, at most every pair of the table, at a
+	// load of 3/4 at most.  Noise, where a label touches most of the others, takes a few doublings.
+	const uint64_t est = std::min<uint64_t>(16ull * n_table, static_cast<uint64_t>(n_table) * (n_table + 1) / 2);
+	uint64_t cap = 1024;
+	while (cap < est + est / 3) cap <<= 1;
+	DevBuf<unsigned long long> keys, counts, out_keys, out_counts;
+	DevBuf<uint32_t> flags;
+	flags.ensure(CONTACT_FLAGS);
+	uint32_t hflags[CONTACT_FLAGS];
+	for (;;) {
+		if (cap > (1ull << 31)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: contacts: more than 2^31 label pairs");
+		keys.ensure(cap); counts.ensure(3 * cap); out_keys.ensure(cap); out_counts.ensure(3 * cap);
+		CKL_HIP(hipMemsetAsync(keys.p, 0xFF, cap * sizeof(unsigned long long), s));
+		CKL_HIP(hipMemsetAsync(counts.p, 0, 3 * cap * sizeof(unsigned long long), s));
+		CKL_HIP(hipMemsetAsync(flags.p, 0, CONTACT_FLAGS * sizeof(uint32_t), s));
+		ContactArgs ca;
+		ca.comp_key = d_comp_key.p;
+		ca.zero_key = d.stats_table[0] == 0 ? 0u : kNoKey;
+		ca.sx = h.sx; ca.n_pixels = static_cast<uint32_t>(d.sxy);
+		ca.keys = keys.p; ca.counts = counts.p;
+		ca.cap_mask = static_cast<uint32_t>(cap - 1);
+		ca.flags = flags.p;
+		hipLaunchKernelGGL(k_run_contacts, dim3((max_runs + kContactRuns - 1) / kContactRuns, ns), dim3(kContactBlock), 0, s,
+			g, ra, d.d_comp_off.p, d.d_ncomp_expect.p, ca);
+		hipLaunchKernelGGL(k_contacts_compact, dim3(static_cast<uint32_t>((cap + kContactCompact - 1) / kContactCompact)), dim3(kBlock), 0, s,
+			keys.p, counts.p, static_cast<uint32_t>(cap), out_keys.p, out_counts.p, flags.p);
+		CKL_HIP(hipMemcpyAsync(hflags, flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+		CKL_HIP(hipStreamSynchronize(s));
+		CKL_HIP(hipGetLastError());
+		if (hflags[CONTACT_BADKEY]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: contacts: a component's label is not in the stream's label table");
+		if (!hflags[CONTACT_FULL]) break;
+		cap <<= 1;
+	}
+	const uint32_t n = hflags[CONTACT_COUNT];
+	std::vector<unsigned long long> k(n), c(3ull * n);
+	if (n) {
+		CKL_HIP(hipMemcpyAsync(k.data(), out_keys.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		CKL_HIP(hipMemcpyAsync(c.data(), out_counts.p, 3ull * n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		CKL_HIP(hipStreamSynchronize(s));
+	}
+	CKL_HIP(hipEventRecord(d.ev[kMaxStages + 1], s));      // the device span of the whole operation, for ckl_decoder_last_timing
+	CKL_HIP(hipEventSynchronize(d.ev[kMaxStages + 1]));
+	CKL_HIP(hipEventElapsedTime(&d.pipeline_ms, d.ev[0], d.ev[kMaxStages + 1]));
+	// keys are (index a << 32 | index b) into the ascending table: their order is that of (a, b).
+	// Bucketed by a (a label touches a few others), then each bucket sorted by b.
+	std::vector<uint32_t> start(n_table + 1, 0), order(n);
+	for (uint32_t i = 0; i < n; i++) start[(k[i] >> 32) + 1]++;
+	for (uint32_t t = 0; t < n_table; t++) start[t + 1] += start[t];
+	{
+		std::vector<uint32_t> at(start.begin(), start.end() - 1);
+		for (uint32_t i = 0; i < n; i++) order[at[k[i] >> 32]++] = i;
+	}
+	for (uint32_t t = 0; t < n_table; t++)
+		std::sort(order.begin() + start[t], order.begin() + start[t + 1], [&](uint32_t x, uint32_t y) { return k[x] < k[y]; });
+	pairs.resize(2ull * n); faces.resize(3ull * n);
+	for (uint32_t i = 0; i < n; i++) {
+		const unsigned long long key = k[order[i]];
+		pairs[2ull * i] = d.stats_table[key >> 32];
+		pairs[2ull * i + 1] = d.stats_table[key & 0xFFFFFFFFull];
+		for (int a = 0; a < 3; a++) faces[3ull * i + a] = c[3ull * order[i] + a];
+	}
+}
+
 // operations::point_cloud (src/operations.hpp:183-262): contours of every component of the decoder's
 // range (ckl_contours.hpp), grouped by label.  The pipeline runs up to the run tables and the
 // component -> label map (the integrity check's mode), then per z-chunk: direction masks, the
@@ -3555,17 +3870,7 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 	// and room are 32-bit: larger slices are refused.
 	const uint64_t raw_worst = 2 * (2 * d.sxy - h.sx - h.sy) + d.sxy;
 	if (raw_worst > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: point_cloud: slices of 2^32 contour nodes or more (5 sx sy - 2 sx - 2 sy) are not supported");
-	{
-		std::vector<uint32_t> errs(ns);
-		decoder_run(d, nullptr, 0, 0, 0, nullptr, false, errs.data());
-		for (uint32_t zi = 0; zi < ns; zi++) {
-			if (!errs[zi]) continue;
-			const std::string z = std::to_string(d.z_start + zi);
-			if (errs[zi] & (ERR_BOC | ERR_RANGE | ERR_CAPACITY)) throw Error(CKL_ERR_RUNTIME, "crackle: crack code is malformed or corrupted on z=" + z);
-			if (errs[zi] & ERR_NCOMP) throw Error(CKL_ERR_RUNTIME, "crackle: component count does not match the label section on z=" + z);
-			throw Error(CKL_ERR_CRC, "crackle: crack code crc mismatch on z=" + z);
-		}
-	}
+	decoder_run_tables(d);
 	RunGeom g;
 	g.planeV = d.d_planes.p; g.planeH = d.d_planes.p + d.plane_words * ns;
 	g.row_words = d.row_words; g.plane_words = d.plane_words;
@@ -4075,6 +4380,26 @@ int ckl_decoder_label_stats(ckl_decoder* d, uint64_t capacity, uint64_t* labels,
 	}
 	catch (const Error& e) { set_last_error(e.what()); return e.status; }
 	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+}
+
+int ckl_decoder_contacts(ckl_decoder* d, uint64_t** pairs, uint64_t** faces, uint64_t* n_pairs) {
+	uint64_t* po = nullptr; uint64_t* fo = nullptr;
+	try {
+		if (!d || !pairs || !faces || !n_pairs) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*pairs = nullptr; *faces = nullptr; *n_pairs = 0;
+		select_device(d->device);
+		wait_for_default_stream(d->stream, d->ev_in);
+		std::vector<uint64_t> p, f;
+		decoder_contacts(*d, p, f);
+		const uint64_t n = p.size() / 2;
+		po = static_cast<uint64_t*>(host_out_alloc(std::max<uint64_t>(2 * n, 1) * 8));
+		fo = static_cast<uint64_t*>(host_out_alloc(std::max<uint64_t>(3 * n, 1) * 8));
+		if (n) { memcpy(po, p.data(), 2 * n * 8); memcpy(fo, f.data(), 3 * n * 8); }
+		*pairs = po; *faces = fo; *n_pairs = n;
+		return CKL_OK;
+	}
+	catch (const Error& e) { set_last_error(e.what()); if (po) host_out_free(po); if (fo) host_out_free(fo); return e.status; }
+	catch (const std::exception& e) { set_last_error(e.what()); if (po) host_out_free(po); if (fo) host_out_free(fo); return CKL_ERR_RUNTIME; }
 }
 
 int ckl_decoder_crack_planes(ckl_decoder* d, const uint32_t** plane_v, const uint32_t** plane_h, uint32_t* row_words, uint64_t* plane_words) {

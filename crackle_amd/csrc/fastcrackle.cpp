@@ -8,7 +8,7 @@
 //
 // Functions: decompress (ref :84-128), compress (:163-210), reencode_markov (:212-227),
 // voxel_counts / centroids / bounding_boxes (:346-426), voxel_connectivity_graph (:538-565),
-// array_equal (:594-618), mode_pooling_2x2x1 (:620-639), point_cloud (:315-345).
+// array_equal (:594-618), mode_pooling_2x2x1 (:620-639), point_cloud (:315-345), contacts (:567-592).
 #include <pybind11/pybind11.h>
 #include <pybind11/numpy.h>
 #include <pybind11/stl.h>
@@ -255,6 +255,35 @@ py::dict point_cloud(const py::buffer buffer, int64_t z_start, int64_t z_end, co
 	return result;
 }
 
+// src/fastcrackle.cpp:567-592: dict (a, b) -> contact area.  operations::contacts' range rule
+// (src/operations.hpp:878-888) first; the device counts faces per axis exactly and the area is the
+// float32 nearest to nx * area_x + ny * area_y + nz * area_z (see crackle_amd.contacts)
+py::dict contacts(const py::buffer buffer, int64_t z_start, int64_t z_end, float wx, float wy, float wz) {
+	Stream s(buffer);
+	const int64_t sz = s.head.sz;
+	z_start = std::max<int64_t>(std::min<int64_t>(z_start, sz - 1), 0);
+	z_end = z_end < 0 ? sz : z_end;
+	z_end = std::max<int64_t>(std::min<int64_t>(z_end, sz), 0);
+	if (z_start >= z_end) throw std::runtime_error("crackle: Invalid range: " + std::to_string(z_start) + " - " + std::to_string(z_end));
+	py::dict result;
+	if (static_cast<uint64_t>(s.head.sx) * s.head.sy == 0) return result;
+	const float ax = wy * wz, ay = wx * wz, az = wx * wy;
+	ckl_decoder* d = nullptr;
+	check(nogil([&] { return ckl_decoder_create(s.p, s.n, z_start, z_end, device(), &d); }));
+	uint64_t* pairs = nullptr; uint64_t* faces = nullptr;
+	uint64_t n = 0;
+	const int rc = nogil([&] { return ckl_decoder_contacts(d, &pairs, &faces, &n); });
+	ckl_decoder_destroy(d);
+	check(rc);
+	for (uint64_t i = 0; i < n; i++) {
+		const double area = static_cast<double>(faces[3 * i]) * ax + static_cast<double>(faces[3 * i + 1]) * ay + static_cast<double>(faces[3 * i + 2]) * az;
+		result[py::make_tuple(py::int_(pairs[2 * i]), py::int_(pairs[2 * i + 1]))] = py::float_(static_cast<float>(area));
+	}
+	if (pairs) ckl_free(pairs);
+	if (faces) ckl_free(faces);
+	return result;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(fastcrackle, m) {
@@ -278,6 +307,8 @@ PYBIND11_MODULE(fastcrackle, m) {
 		py::arg("buffer"), py::arg("z_start") = 0, py::arg("z_end") = -1, py::arg("parallel") = 1);
 	m.def("point_cloud", &point_cloud, "Extract one or more point clouds without decompressing.",
 		py::arg("buffer"), py::arg("z_start") = 0, py::arg("z_end") = -1, py::arg("labels") = py::none(), py::arg("skip_background") = false, py::arg("parallel") = 1);
+	m.def("contacts", &contacts, "Extract the 6-connected contact areas between labels.",
+		py::arg("buffer"), py::arg("z_start") = 0, py::arg("z_end") = -1, py::arg("wx") = 1.0, py::arg("wy") = 1.0, py::arg("wz") = 1.0);
 	m.def("voxel_connectivity_graph", &voxel_connectivity_graph, "Extract the voxel connectivity graph from the image.",
 		py::arg("buffer"), py::arg("z_start") = 0, py::arg("z_end") = -1, py::arg("parallel") = 1, py::arg("connectivity") = 4);
 }

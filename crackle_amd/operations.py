@@ -1,6 +1,7 @@
 """Stream surgery on .ckl bytes without decoding — the slab merge the sharded encoder is built
 on, exposed with the reference's names (crackle/operations.py:424-662: zstack, zsplit,
-zshatter).  Host only (native: ckl_zstack / ckl_zsplit); FLAT label streams."""
+zshatter).  Host only (native: ckl_zstack / ckl_zsplit); FLAT label streams.  The consumers
+array_equal, mode_pooling_2x2x1, point_cloud and contacts run on the device."""
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -176,3 +177,62 @@ def point_cloud(
   if scalar_input:
     return ptc[label[0]]
   return ptc
+
+
+def _contacts_counts(binary: bytes, z_start: int = 0, z_end: int = -1, device: int = 0):
+  """ckl_decoder_contacts over the range, clamped by operations::contacts' rule first
+  (src/operations.hpp:878-888): (pairs uint64 [n, 2], faces uint64 [n, 3]), ascending by (a, b)."""
+  b = bytes(binary)
+  head = header(b)
+  sz = int(head.sz)
+  zs = max(min(int(z_start), sz - 1), 0)
+  ze = sz if z_end < 0 else int(z_end)
+  ze = max(min(ze, sz), 0)
+  if zs >= ze:
+    raise RuntimeError(f"crackle: Invalid range: {zs} - {ze}")
+  empty = (np.zeros((0, 2), np.uint64), np.zeros((0, 3), np.uint64))
+  if int(head.sx) * int(head.sy) == 0:
+    return empty
+  L = _lib.lib()
+  handle = C.c_void_p()
+  if L.ckl_decoder_create(b, len(b), zs, ze, int(device), C.byref(handle)) != _lib.CKL_OK:
+    raise RuntimeError(_lib.last_error())
+  pp, fp, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+  try:
+    if L.ckl_decoder_contacts(handle, C.byref(pp), C.byref(fp), C.byref(n)) != _lib.CKL_OK:
+      raise RuntimeError(_lib.last_error())
+    k = int(n.value)
+    if k == 0:
+      return empty
+    pairs = np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_uint64)), shape=(k, 2)).copy()
+    faces = np.ctypeslib.as_array(C.cast(fp, C.POINTER(C.c_uint64)), shape=(k, 3)).copy()
+    return pairs, faces
+  finally:
+    for p in (pp, fp):
+      if p.value:
+        L.ckl_free(p)
+    L.ckl_decoder_destroy(handle)
+
+
+def contacts(
+  binary: bytes, anisotropy: Tuple[float, float, float] = (1.0, 1.0, 1.0), device: int = 0,
+) -> Dict[Tuple[int, int], float]:
+  """6-connected contact area between touching labels (crackle/operations.py:956-964,
+  src/operations.hpp:850-1021): {(a, b): area} with a <= b as uint64 (signed labels
+  sign-extended, so -1 is 2**64 - 1); label 0 is left out.  In-plane faces count between
+  different components of a slice, so a stream whose label table was rewritten without
+  re-encoding reports pairs (a, a); z faces count between different labels.
+
+  One difference from the reference, on purpose: the device counts the faces of every pair per
+  axis exactly, and the area is the float32 nearest to nx*wy*wz + ny*wx*wz + nz*wx*wy (face
+  areas as float32 products of the float32 weights, the sum in float64).  The reference adds one
+  float32 per face; both agree wherever its running sum is exact (integer or dyadic weights
+  below 2^24 units of the smallest face), and beyond that the reference's sum rounds or stalls
+  (at 16777216.0 with unit weights) where this one does not."""
+  wx, wy, wz = (np.float32(w) for w in anisotropy)
+  ax, ay, az = float(np.float32(wy * wz)), float(np.float32(wx * wz)), float(np.float32(wx * wy))
+  pairs, faces = _contacts_counts(binary, 0, -1, device)
+  out = {}
+  for (a, b), (nx, ny, nz) in zip(pairs.tolist(), faces.tolist()):
+    out[(a, b)] = float(np.float32(nx * ax + ny * ay + nz * az))
+  return out

@@ -191,6 +191,21 @@ int ckl_mode_pooling_2x2x1(
 int ckl_decoder_label_stats(
 	ckl_decoder* d, uint64_t capacity, uint64_t* labels, uint64_t* counts,
 	uint64_t* sums, uint32_t* boxes, uint64_t* n_labels);
+/* Contact faces between touching labels in the decoder's z-range without materialising the
+ * volume: replaces crackle::operations::contacts (src/operations.hpp:850-1021, bound as
+ * fastcrackle.contacts, src/fastcrackle.cpp:567-592).  A face between (x,y) and (x+1,y) or
+ * (x,y+1) of one slice counts when the two pixels lie in different components of that slice
+ * (:950-961, :995-1008: a stream whose label table was rewritten may have touching components of
+ * one label, reported as the pair (a, a)); a face between (x,y,z-1) and (x,y,z) counts for z past
+ * the first slice of the range when the two labels differ (:963, :1009-1015); faces with a label
+ * 0 are dropped (:940-948).  Labels are the values the decoder paints, sign-extended to 64 bits
+ * (decode_label_map<uint64_t>, src/crackle.hpp:456-476).  The range is the session's: callers
+ * that follow the reference clamp it by its rule first (:878-888).  Host outputs owned by the
+ * library, released with ckl_free: *pairs holds 2 * *n_pairs values (a <= b as unsigned),
+ * ascending by (a, b); *faces holds 3 * *n_pairs exact face counts (x, y, z) per pair.  The
+ * reference adds one float32 area per face instead; areas are the caller's (nx * wy * wz +
+ * ny * wx * wz + nz * wx * wy). */
+int ckl_decoder_contacts(ckl_decoder* d, uint64_t** pairs, uint64_t** faces, uint64_t* n_pairs);
 /* Elapsed device time of the last run, from HIP events recorded on the library's
  * own stream around (a) the whole pipeline and (b) the dominant kernel. */
 int ckl_decoder_last_timing(const ckl_decoder* d, float* pipeline_ms, float* dominant_kernel_ms);

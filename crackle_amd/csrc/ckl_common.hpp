@@ -169,6 +169,12 @@ int select_device(int device);   // throws CKL_ERR_NO_DEVICE
 // clear the buffers they hand over on the default stream.
 void wait_for_default_stream(hipStream_t s, hipEvent_t scratch_event);
 
+// The stream `buf` with every 2D component given a new value (ckl_zstack.hip): uint32, FLAT labels,
+// `uniq` the ascending values, keys[i] (key_width bytes each, n_keys of them: one per component in
+// stream order) the index of component i's value in uniq.  Everything but header and label section is
+// copied.  Host only; the result is malloc'd (release with ckl_free).
+uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len);
+
 // markov model tables (src/markov.hpp:43-68, 222-266, 325-420)
 extern const uint8_t kMarkovLUT[24];
 std::vector<uint8_t> markov_model_from_stored(const uint8_t* stream, uint64_t nbytes, int order);   // rows x 4, rank -> symbol

@@ -1,0 +1,271 @@
+// 3D connected components from the run tables: the device half of connected_components.
+// (Included by ckl_decode.hip inside namespace ckl, after the contacts kernels whose run walk and
+// constants it shares: kContactBlock / kContactPer / kContactRuns, kNoKey.)
+//
+// The crack codes of a slice already describe its 4-connected components, and the decoder numbers
+// them in the order of their first raster pixel.  A 3D component of a label is a union of those 2D
+// components: nothing has to be painted, the components only have to be LINKED wherever two of them
+// with the same label hold neighbouring voxels, and the sets numbered.
+//
+//   k_cc_init      parent[c] = c over the global component ids (slice offset + id in the slice)
+//   k_run_links    one run per thread (the layout of k_run_contacts): the runs of the neighbouring
+//                  rows are walked through word_base and the vertical-crack plane; where the label
+//                  is the same and is not 0 the two components are united.
+//   k_cc_flatten   root of every component (its set's smallest id)
+//   k_cc_count / k_cc_offsets / k_cc_number
+//                  device-wide exclusive scan over the roots with a nonzero label: a root's number
+//                  is 1 + its rank.  Global ids ascend with (z, first raster pixel), so a set's
+//                  smallest id belongs to the component that holds the set's first voxel in
+//                  x-fastest, then y, then z order, and the ranks of the roots are the numbering by
+//                  first voxel.
+//   k_cc_keys      every component's key into the new unique list, packed at the key width
+//
+// Rows and x ranges looked at from the run [x0, x1] of row y in slice z (clamped to the slice):
+//
+//   connectivity   same slice                              previous slice
+//   6              next run of the row; row y-1 [x0, x1]     row y [x0, x1]
+//   18             next run; row y-1 [x0-1, x1+1]            row y [x0-1, x1+1]; rows y-1, y+1 [x0, x1]
+//   26             as 18                                     rows y-1, y, y+1 [x0-1, x1+1]
+//
+// The later run of every neighbouring pair does the looking (rows above, the slice before), so each
+// pair is seen once.  In the same slice two different components with one label only exist in a
+// stream whose label table was rewritten without re-encoding; they are united too.
+//
+// Union-find without locks: parents only ever decrease.  unite() hooks the larger of two roots
+// under the smaller with atomicMin and goes on with the value it displaced, so whatever the order in
+// which the atomics land, a set's root ends up as its smallest member: the result does not depend on
+// scheduling.
+#pragma once
+
+enum : uint32_t { CC_BADKEY = 0, CC_HAS_ZERO = 1, CC_COUNT = 2, CC_FLAGS = 4 };
+
+struct LinkArgs {
+	const uint32_t* comp_key;        // [total_comp] label table index of every component (kNoKey: not in the table)
+	uint32_t zero_key;               // table index of label 0 (kNoKey: absent): background, never linked
+	uint32_t sx, sy, n_pixels;
+	uint32_t connectivity;           // 6, 18 or 26
+	uint32_t* parent;                // [total_comp]
+	uint32_t* flags;                 // [CC_FLAGS]
+};
+
+__device__ __forceinline__ uint32_t cc_parent(const uint32_t* parent, uint32_t x) {
+	return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ uint32_t cc_find(const uint32_t* parent, uint32_t x) {
+	for (;;) {
+		const uint32_t p = cc_parent(parent, x);
+		if (p == x) return x;
+		x = p;
+	}
+}
+
+// An ancestor of x from ordinary (cached) loads.  A value read late is still a value parent[x] once
+// held, and whatever x pointed at stays in x's set: the walk ends at a member of the set at or above
+// the root it would have found then, and cc_unite goes on from there with loads that see the atomics.
+__device__ __forceinline__ uint32_t cc_walk_cached(const uint32_t* parent, uint32_t x) {
+	for (;;) {
+		const uint32_t p = parent[x];
+		if (p == x) return x;
+		x = p;
+	}
+}
+
+// unites the sets of a and b; a (the caller's stand-in for its own component) becomes the root found,
+// so that the thread's next link starts where this one ended
+__device__ __forceinline__ void cc_unite(uint32_t* parent, uint32_t& a, uint32_t b) {
+	a = cc_walk_cached(parent, a);
+	b = cc_walk_cached(parent, b);
+	while (a != b) {
+		a = cc_find(parent, a);
+		b = cc_find(parent, b);
+		if (a == b) break;
+		if (a < b) { const uint32_t t = a; a = b; b = t; }
+		// a > b: hook a under b.  A displaced parent other than a itself means somebody hooked a in
+		// the meantime: a now points at min(old, b), and old and b are still to be united.
+		const uint32_t old = atomicMin(parent + a, b);
+		if (old == a) { a = b; break; }
+		a = old;
+	}
+}
+
+// links between the run's pixels [lo, hi] (a member ga of its component's set, label index ka) and the runs of row
+// y of slice zj; skip: the run's own component where zj is its slice (kNoKey otherwise)
+__device__ __forceinline__ void link_row(
+	const RunGeom& g, const RunArrays& r, const LinkArgs& la,
+	uint32_t zj, const uint32_t* key_j, uint32_t nce_j, uint32_t off_j, uint32_t y, uint32_t lo, uint32_t hi,
+	uint32_t skip, uint32_t& ga, uint32_t ka, uint32_t& last
+) {
+	const uint64_t rb = r.rbase[zj];
+	const uint32_t nj = r.nruns[zj];
+	const uint32_t row = y * la.sx;
+	const uint32_t w = lo >> 5;
+	uint32_t j = r.word_base[zj * g.plane_words + y * g.row_words + w] + __popc(g.breaks(zj, y, w) & mask_le(lo & 31u)) - 1u;
+	while (j < nj) {
+		// the run after the last one of a row starts the next row (or the slice ends): e <= sx
+		const uint32_t e = (j + 1 < nj ? r.run_start[rb + j + 1] : la.n_pixels) - row;
+		const uint32_t ccj = r.run_cc[rb + j];
+		if (ccj != skip) {
+			const uint32_t kj = ccj < nce_j ? key_j[ccj] : kNoKey;
+			if (kj == kNoKey) atomicOr(la.flags + CC_BADKEY, 1u);
+			else if (kj == ka && off_j + ccj != last) {
+				last = off_j + ccj;
+				cc_unite(la.parent, ga, last);
+			}
+		}
+		if (e > hi) return;
+		j++;
+	}
+	atomicOr(la.flags + CC_BADKEY, 1u);      // the run tables do not cover the row
+}
+
+// grid = (ceil(most runs of a slice / kContactRuns), nslices), block = kContactBlock
+static __global__ void __launch_bounds__(kContactBlock) k_run_links(
+	RunGeom g, RunArrays r, const uint64_t* __restrict__ comp_off, const uint32_t* __restrict__ ncomp_expect, LinkArgs la
+) {
+	const uint32_t zi = blockIdx.y;
+	const uint32_t n = r.nruns[zi];
+	const uint32_t i0 = blockIdx.x * kContactRuns;
+	if (i0 >= n) return;
+	const uint64_t rb = r.rbase[zi];
+	const uint32_t nce = ncomp_expect[zi];
+	const uint32_t off = static_cast<uint32_t>(comp_off[zi]);
+	const uint32_t* key_z = la.comp_key + off;
+	const uint32_t nce_p = zi ? ncomp_expect[zi - 1] : 0u;
+	const uint32_t off_p = zi ? static_cast<uint32_t>(comp_off[zi - 1]) : 0u;
+	const uint32_t* key_p = la.comp_key + off_p;
+	const bool diag = la.connectivity != 6;
+	const bool corners = la.connectivity == 26;
+	for (uint32_t k = 0; k < kContactPer; k++) {
+		const uint32_t i = i0 + k * kContactBlock + threadIdx.x;
+		if (i >= n) break;
+		const uint32_t a = r.run_start[rb + i];
+		const uint32_t b = i + 1 < n ? r.run_start[rb + i + 1] : la.n_pixels;
+		const uint32_t cc = r.run_cc[rb + i];
+		const uint32_t y = a / la.sx;
+		const uint32_t row = y * la.sx;
+		const uint32_t x0 = a - row, x1 = b - 1 - row;
+		const uint32_t ka = cc < nce ? key_z[cc] : kNoKey;
+		if (ka == kNoKey) { atomicOr(la.flags + CC_BADKEY, 1u); continue; }
+		if (ka == la.zero_key) continue;
+		uint32_t ga = off + cc;      // the component, then the highest member of its set that a link has found
+		uint32_t last = ga;          // the component of the link this thread made last: the same again is skipped
+		if (b < row + la.sx) {      // the next run is in the same row
+			const uint32_t cc2 = r.run_cc[rb + i + 1];
+			if (cc2 != cc) {
+				const uint32_t kb = cc2 < nce ? key_z[cc2] : kNoKey;
+				if (kb == kNoKey) atomicOr(la.flags + CC_BADKEY, 1u);
+				else if (kb == ka) { last = off + cc2; cc_unite(la.parent, ga, last); }
+			}
+		}
+		const uint32_t xl = x0 ? x0 - 1 : 0u, xr = min(x1 + 1, la.sx - 1);      // [x0 - 1, x1 + 1] inside the slice
+		if (y > 0) link_row(g, r, la, zi, key_z, nce, off, y - 1, diag ? xl : x0, diag ? xr : x1, cc, ga, ka, last);
+		if (zi == 0) continue;
+		link_row(g, r, la, zi - 1, key_p, nce_p, off_p, y, diag ? xl : x0, diag ? xr : x1, kNoKey, ga, ka, last);
+		if (!diag) continue;
+		if (y > 0) link_row(g, r, la, zi - 1, key_p, nce_p, off_p, y - 1, corners ? xl : x0, corners ? xr : x1, kNoKey, ga, ka, last);
+		if (y + 1 < la.sy) link_row(g, r, la, zi - 1, key_p, nce_p, off_p, y + 1, corners ? xl : x0, corners ? xr : x1, kNoKey, ga, ka, last);
+	}
+}
+
+static __global__ void __launch_bounds__(kBlock) k_cc_init(uint32_t* __restrict__ parent, uint32_t n) {
+	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+	if (c < n) parent[c] = c;
+}
+
+// root[c] = the smallest id of c's set (parent is read only: nothing moves under the walk)
+static __global__ void __launch_bounds__(kBlock) k_cc_flatten(const uint32_t* __restrict__ parent, uint32_t n, uint32_t* __restrict__ root) {
+	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+	if (c >= n) return;
+	uint32_t x = c, p = parent[c];
+	while (p != x) { x = p; p = parent[x]; }
+	root[c] = x;
+}
+
+// The scan over the numbered roots, kCcPer components per thread: counts per workgroup, their
+// exclusive prefix (one workgroup), then the numbers.
+constexpr uint32_t kCcPer = 4;
+constexpr uint32_t kCcTile = kBlock * kCcPer;
+
+__device__ __forceinline__ uint32_t cc_numbered(const uint32_t* root, const uint32_t* comp_key, uint32_t zero_key, uint32_t c, uint32_t n) {
+	return (c < n && root[c] == c && comp_key[c] != zero_key) ? 1u : 0u;
+}
+
+static __global__ void __launch_bounds__(kBlock) k_cc_count(
+	const uint32_t* __restrict__ root, const uint32_t* __restrict__ comp_key, uint32_t zero_key, uint32_t n,
+	uint32_t* __restrict__ blk, uint32_t* __restrict__ flags
+) {
+	__shared__ uint32_t s_red[kWaves];
+	const uint32_t c0 = blockIdx.x * kCcTile + threadIdx.x * kCcPer;
+	uint32_t cnt = 0, zero = 0;
+#pragma unroll
+	for (uint32_t j = 0; j < kCcPer; j++) {
+		cnt += cc_numbered(root, comp_key, zero_key, c0 + j, n);
+		zero |= (c0 + j < n && comp_key[c0 + j] == zero_key) ? 1u : 0u;
+	}
+	if (zero) atomicOr(flags + CC_HAS_ZERO, 1u);
+	cnt = block_sum(cnt, s_red);
+	if (threadIdx.x == 0) blk[blockIdx.x] = cnt;
+}
+
+// grid = 1
+static __global__ void __launch_bounds__(kBlock) k_cc_offsets(uint32_t* __restrict__ blk, uint32_t nb, uint32_t* __restrict__ flags) {
+	__shared__ uint32_t s_scan[kWaves];
+	uint32_t carry = 0;
+	for (uint32_t b0 = 0; b0 < nb; b0 += kBlock) {
+		const uint32_t b = b0 + threadIdx.x;
+		uint32_t v[1] = { b < nb ? blk[b] : 0u }, tot[1];
+		block_excl_add<1>(v, tot, s_scan);
+		if (b < nb) blk[b] = carry + v[0];
+		carry += tot[0];
+	}
+	if (threadIdx.x == 0) flags[CC_COUNT] = carry;
+}
+
+// number[c] = 1 + rank for the numbered roots (others are not written); root_label[rank] = the root's label
+static __global__ void __launch_bounds__(kBlock) k_cc_number(
+	const uint32_t* __restrict__ root, const uint32_t* __restrict__ comp_key, uint32_t zero_key, uint32_t n,
+	const uint32_t* __restrict__ blk, uint32_t* __restrict__ number,
+	const uint64_t* __restrict__ label_map, uint64_t* __restrict__ root_label
+) {
+	__shared__ uint32_t s_scan[kWaves];
+	const uint32_t c0 = blockIdx.x * kCcTile + threadIdx.x * kCcPer;
+	uint32_t f[kCcPer], v[1] = { 0 }, tot[1];
+#pragma unroll
+	for (uint32_t j = 0; j < kCcPer; j++) {
+		f[j] = cc_numbered(root, comp_key, zero_key, c0 + j, n);
+		v[0] += f[j];
+	}
+	block_excl_add<1>(v, tot, s_scan);
+	uint32_t at = blk[blockIdx.x] + v[0];
+#pragma unroll
+	for (uint32_t j = 0; j < kCcPer; j++) {
+		if (!f[j]) continue;
+		if (root_label) root_label[at] = label_map[c0 + j];
+		number[c0 + j] = ++at;
+	}
+}
+
+// keys[c] = index of c's new value in the unique list (0, 1 .. N with a zero label somewhere, else
+// 1 .. N), at the width of the list's length: four components per thread, one store
+static __global__ void __launch_bounds__(kBlock) k_cc_keys(
+	const uint32_t* __restrict__ root, const uint32_t* __restrict__ comp_key, uint32_t zero_key, uint32_t n,
+	const uint32_t* __restrict__ number, const uint32_t* __restrict__ flags, uint8_t* __restrict__ keys
+) {
+	static_assert(kCcPer == 4, "one 4-, 8- or 16-byte store per thread");
+	const uint32_t c0 = (blockIdx.x * kBlock + threadIdx.x) * 4u;
+	if (c0 >= n) return;
+	const uint32_t has_zero = flags[CC_HAS_ZERO];
+	const uint64_t n_unique = static_cast<uint64_t>(flags[CC_COUNT]) + has_zero;
+	uint32_t k[4];
+#pragma unroll
+	for (uint32_t j = 0; j < 4; j++) {
+		const uint32_t c = c0 + j;
+		k[j] = 0;
+		if (c < n && comp_key[c] != zero_key) k[j] = number[root[c]] - (has_zero ? 0u : 1u);
+	}
+	// the buffer is padded to a multiple of four keys
+	if (n_unique <= 0xFFull) *reinterpret_cast<uchar4*>(keys + c0) = make_uchar4(static_cast<unsigned char>(k[0]), static_cast<unsigned char>(k[1]), static_cast<unsigned char>(k[2]), static_cast<unsigned char>(k[3]));
+	else if (n_unique <= 0xFFFFull) *reinterpret_cast<ushort4*>(keys + 2ull * c0) = make_ushort4(static_cast<unsigned short>(k[0]), static_cast<unsigned short>(k[1]), static_cast<unsigned short>(k[2]), static_cast<unsigned short>(k[3]));
+	else *reinterpret_cast<uint4*>(keys + 4ull * c0) = make_uint4(k[0], k[1], k[2], k[3]);
+}

@@ -32,6 +32,8 @@
 //   k_run_stats       per-label voxel counts, coordinate sums and boxes from the runs
 //   k_run_contacts    faces between touching labels per axis from the runs (contacts)
 //   k_contacts_compact  the occupied entries of its pair table, packed
+//   k_run_links       3D connected components: 2D components with one label united across rows,
+//                     diagonals and slices (ckl_components3d.hpp, with k_cc_* that number the sets)
 //   k_vcg             voxel connectivity graph from the planes (+ labels for the z bits)
 #include "ckl_common.hpp"
 #include "ckl_runs.hpp"
@@ -1744,6 +1746,8 @@ static __global__ void __launch_bounds__(kBlock) k_contacts_compact(
 		at++;
 	}
 }
+
+#include "ckl_components3d.hpp"
 
 // ------------------------------------------------------------------------------
 // paint (crackle.hpp:617-656): out[p] = label of p's run
@@ -3842,6 +3846,86 @@ void decoder_contacts(ckl_decoder& d, std::vector<uint64_t>& pairs, std::vector<
 	}
 }
 
+// connected_components over the whole stream (ckl_components3d.hpp): one pipeline run up to the run
+// tables and the component -> label map, the links, the numbering.  keys: one key per component at
+// key_width bytes into the list 0, 1 .. n_components (has_zero) or 1 .. n_components;
+// root_labels (when wanted): the original label of every numbered component.
+struct Components3D {
+	std::vector<uint8_t> keys;
+	int key_width = 1;
+	uint64_t n_components = 0;
+	bool has_zero = false;
+	std::vector<uint64_t> root_labels;
+};
+
+void decoder_connected_components(ckl_decoder& d, int connectivity, bool want_labels, Components3D& out) {
+	const Header& h = d.head;
+	hipStream_t s = d.stream;
+	const uint32_t ns = d.nslices;
+	decoder_run_tables(d);
+	ensure_label_table(d);
+	const uint32_t n_table = static_cast<uint32_t>(d.stats_table.size());
+	if (d.total_comp == 0 || n_table == 0) throw Error(CKL_ERR_RUNTIME, "crackle: label section is malformed or corrupted.");
+	if (d.total_comp > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: connected_components: more than 2^32 - 1 components");
+	const uint32_t nc = static_cast<uint32_t>(d.total_comp);
+	DevBuf<uint32_t> d_comp_key, parent, root, number, blk, flags;
+	DevBuf<uint64_t> root_label;
+	DevBuf<uint8_t> keys;
+	d_comp_key.ensure(nc);
+	hipLaunchKernelGGL(k_component_label_index, dim3((nc + 255) / 256), dim3(256), 0, s,
+		d.d_label_map.p, d.total_comp, d.d_stats_table.p, n_table, d_comp_key.p);
+	std::vector<uint32_t> nruns(ns);
+	CKL_HIP(hipMemcpyAsync(nruns.data(), d.d_nruns.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	const uint32_t max_runs = *std::max_element(nruns.begin(), nruns.end());
+
+	RunGeom g;
+	g.planeV = d.d_planes.p; g.planeH = d.d_planes.p + d.plane_words * ns;
+	g.row_words = d.row_words; g.plane_words = d.plane_words;
+	g.flip = (h.crack_format == IMPERMISSIBLE) ? 1u : 0u;
+	g.sx = h.sx; g.sy = h.sy;
+	RunArrays ra;
+	ra.word_base = d.d_word_base.p; ra.rbase = d.d_rbase.p; ra.rcap = d.d_rcap.p;
+	ra.parent = d.d_parent.p; ra.run_start = d.d_run_start.p; ra.run_cc = d.d_run_cc.p;
+	ra.nruns = d.d_nruns.p; ra.ncomp = d.d_ncomp.p; ra.slice_err = d.d_slice_err.p;
+
+	const uint32_t nb = (nc + kCcTile - 1) / kCcTile;
+	parent.ensure(nc); root.ensure(nc); number.ensure(nc); blk.ensure(nb); flags.ensure(CC_FLAGS);
+	if (want_labels) root_label.ensure(nc);
+	keys.ensure(4ull * nb * kCcTile);      // the widest keys, padded to whole tiles
+	CKL_HIP(hipMemsetAsync(flags.p, 0, CC_FLAGS * sizeof(uint32_t), s));
+	LinkArgs la;
+	la.comp_key = d_comp_key.p;
+	la.zero_key = d.stats_table[0] == 0 ? 0u : kNoKey;
+	la.sx = h.sx; la.sy = h.sy; la.n_pixels = static_cast<uint32_t>(d.sxy);
+	la.connectivity = static_cast<uint32_t>(connectivity);
+	la.parent = parent.p; la.flags = flags.p;
+	hipLaunchKernelGGL(k_cc_init, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, parent.p, nc);
+	if (max_runs) hipLaunchKernelGGL(k_run_links, dim3((max_runs + kContactRuns - 1) / kContactRuns, ns), dim3(kContactBlock), 0, s,
+		g, ra, d.d_comp_off.p, d.d_ncomp_expect.p, la);
+	hipLaunchKernelGGL(k_cc_flatten, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, parent.p, nc, root.p);
+	hipLaunchKernelGGL(k_cc_count, dim3(nb), dim3(kBlock), 0, s, root.p, d_comp_key.p, la.zero_key, nc, blk.p, flags.p);
+	hipLaunchKernelGGL(k_cc_offsets, dim3(1), dim3(kBlock), 0, s, blk.p, nb, flags.p);
+	hipLaunchKernelGGL(k_cc_number, dim3(nb), dim3(kBlock), 0, s, root.p, d_comp_key.p, la.zero_key, nc, blk.p, number.p,
+		d.d_label_map.p, want_labels ? reinterpret_cast<uint64_t*>(root_label.p) : nullptr);
+	hipLaunchKernelGGL(k_cc_keys, dim3(nb), dim3(kBlock), 0, s, root.p, d_comp_key.p, la.zero_key, nc, number.p, flags.p, keys.p);
+	uint32_t hflags[CC_FLAGS];
+	CKL_HIP(hipMemcpyAsync(hflags, flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	CKL_HIP(hipGetLastError());
+	if (hflags[CC_BADKEY]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: connected_components: a component's label is not in the stream's label table");
+	out.n_components = hflags[CC_COUNT];
+	out.has_zero = hflags[CC_HAS_ZERO] != 0;
+	out.key_width = byte_width(out.n_components + (out.has_zero ? 1 : 0));
+	out.keys.resize(static_cast<size_t>(nc) * out.key_width);
+	CKL_HIP(hipMemcpyAsync(out.keys.data(), keys.p, out.keys.size(), hipMemcpyDeviceToHost, s));
+	out.root_labels.resize(want_labels ? out.n_components : 0);
+	if (want_labels && out.n_components) CKL_HIP(hipMemcpyAsync(out.root_labels.data(), root_label.p, out.n_components * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipEventRecord(d.ev[kMaxStages + 1], s));      // the device span of the whole operation, for ckl_decoder_last_timing
+	CKL_HIP(hipEventSynchronize(d.ev[kMaxStages + 1]));
+	CKL_HIP(hipEventElapsedTime(&d.pipeline_ms, d.ev[0], d.ev[kMaxStages + 1]));
+}
+
 // operations::point_cloud (src/operations.hpp:183-262): contours of every component of the decoder's
 // range (ckl_contours.hpp), grouped by label.  The pipeline runs up to the run tables and the
 // component -> label map (the integrity check's mode), then per z-chunk: direction masks, the
@@ -4400,6 +4484,45 @@ int ckl_decoder_contacts(ckl_decoder* d, uint64_t** pairs, uint64_t** faces, uin
 	}
 	catch (const Error& e) { set_last_error(e.what()); if (po) host_out_free(po); if (fo) host_out_free(fo); return e.status; }
 	catch (const std::exception& e) { set_last_error(e.what()); if (po) host_out_free(po); if (fo) host_out_free(fo); return CKL_ERR_RUNTIME; }
+}
+
+int ckl_connected_components(
+	const uint8_t* buf, uint64_t n, int connectivity, int device,
+	uint8_t** out, uint64_t* out_len, uint64_t** component_labels, uint64_t* n_components
+) {
+	ckl_decoder* d = nullptr;
+	uint64_t* lo = nullptr;
+	try {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*out = nullptr; *out_len = 0;
+		if (component_labels) *component_labels = nullptr;
+		if (n_components) *n_components = 0;
+		if (connectivity != 6 && connectivity != 18 && connectivity != 26) throw Error(CKL_ERR_ARG, "crackle_amd: connected_components: connectivity must be 6, 18 or 26");
+		const Header h = Header::parse(buf, n);
+		if (h.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: connected components need a version 1 stream: version 0 has no crack crcs to carry over");
+		Components3D cc;
+		std::vector<uint64_t> uniq;
+		if (h.voxels() != 0) {      // (an empty volume: its header, from the host alone)
+			const int rc = ckl_decoder_create(buf, n, 0, -1, device, &d);
+			if (rc != CKL_OK) return rc;
+			select_device(d->device);
+			wait_for_default_stream(d->stream, d->ev_in);
+			decoder_connected_components(*d, connectivity, component_labels != nullptr, cc);
+			ckl_decoder_destroy(d); d = nullptr;
+			uniq.resize(cc.n_components + (cc.has_zero ? 1 : 0));
+			for (uint64_t i = 0; i < uniq.size(); i++) uniq[i] = i + (cc.has_zero ? 0 : 1);
+		}
+		if (component_labels) {
+			lo = static_cast<uint64_t*>(host_out_alloc(std::max<uint64_t>(cc.n_components, 1) * 8));
+			if (cc.n_components) memcpy(lo, cc.root_labels.data(), cc.n_components * 8);
+		}
+		*out = relabel_stream(buf, n, uniq, cc.keys.data(), cc.key_width, cc.keys.size() / cc.key_width, out_len);
+		if (component_labels) *component_labels = lo;
+		if (n_components) *n_components = cc.n_components;
+		return CKL_OK;
+	}
+	catch (const Error& e) { set_last_error(e.what()); ckl_decoder_destroy(d); if (lo) host_out_free(lo); return e.status; }
+	catch (const std::exception& e) { set_last_error(e.what()); ckl_decoder_destroy(d); if (lo) host_out_free(lo); return CKL_ERR_RUNTIME; }
 }
 
 int ckl_decoder_crack_planes(ckl_decoder* d, const uint32_t** plane_v, const uint32_t** plane_h, uint32_t* row_words, uint64_t* plane_words) {

@@ -210,3 +210,123 @@ extern "C" int ckl_zsplit(const uint8_t* buf, uint64_t n, int64_t z_start, int64
 	catch (const Error& e) { set_last_error(e.what()); return e.status; }
 	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
 }
+
+// ------------------------------------------------------------------------------
+// Relabelling by 2D component (connected_components): the crack codes of a stream already
+// describe the 4-connected components of every slice, so giving every component a new value
+// changes the label section and the header only.  z-index, markov model, crack codes and the
+// per-slice crcs (taken over the component image) are copied.
+// ------------------------------------------------------------------------------
+namespace ckl {
+
+// the per-slice component counts of a version 1 stream, FLAT or pins (labels.hpp:424-451, 453-617)
+static const uint8_t* component_counts(const Header& h, const uint8_t* buf, uint64_t n, uint64_t* total) {
+	if (h.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: connected components need a version 1 stream: version 0 has no crack crcs to carry over");
+	if (!h.layout_fits(n)) throw Error(CKL_ERR_RUNTIME, "crackle: Unable to read past end of buffer.");
+	const uint8_t* lb = buf + h.header_bytes() + h.grid_index_bytes();
+	const uint64_t nlb = h.num_label_bytes;
+	const uint64_t sw = static_cast<uint64_t>(h.stored_data_width);
+	uint64_t head;      // bytes in front of the unique list
+	if (h.label_format == FLAT) head = 8;
+	else if (h.label_format == PINS_VARIABLE_WIDTH) head = sw + 8;
+	else throw Error(CKL_ERR_RUNTIME, "crackle: Unsupported label format. Got: " + std::to_string(h.label_format));
+	if (nlb < head) throw Error(CKL_ERR_RUNTIME, "crackle: label section is malformed or corrupted.");
+	const uint64_t num_unique = rd_le(lb + head - 8, 8);
+	if (num_unique > (nlb - head) / sw) throw Error(CKL_ERR_RUNTIME, "crackle: label section is malformed or corrupted.");
+	const uint64_t offset = head + sw * num_unique;
+	const uint64_t sxy = static_cast<uint64_t>(h.sx) * h.sy;
+	const int cw = byte_width(sxy);
+	if (static_cast<uint64_t>(cw) * h.sz > nlb - offset) throw Error(CKL_ERR_RUNTIME, "crackle: label section is malformed or corrupted.");
+	uint64_t t = 0;
+	for (uint64_t z = 0; z < h.sz; z++) {
+		const uint64_t c = rd_le(lb + offset + z * cw, cw);
+		if (c > sxy) throw Error(CKL_ERR_RUNTIME, "crackle: label section is malformed or corrupted.");
+		t += c;
+	}
+	*total = t;
+	return lb + offset;
+}
+
+uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len) {
+	const Header h0 = Header::parse(buf, n);
+	Header h = h0;
+	h.format_version = 1;
+	h.data_width = 4;
+	h.is_signed = false;
+	h.label_format = FLAT;
+	h.is_sorted = true;
+	h.stored_data_width = byte_width(uniq.empty() ? 0 : uniq.back());
+	h.num_label_bytes = 0;
+	std::vector<uint8_t> hb;
+	if (h0.voxels() == 0) {
+		// crackle.hpp:96-98: the stream of an empty volume is its header
+		if (h0.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: connected components need a version 1 stream: version 0 has no crack crcs to carry over");
+		h.stored_data_width = 1;
+		h.write(hb);
+		uint8_t* o = static_cast<uint8_t*>(malloc(hb.size()));
+		if (!o) throw Error(CKL_ERR_RUNTIME, "crackle_amd: out of host memory");
+		memcpy(o, hb.data(), hb.size());
+		*out_len = hb.size();
+		return o;
+	}
+	uint64_t total_comp = 0;
+	const uint8_t* counts = component_counts(h0, buf, n, &total_comp);
+	if (n_keys != total_comp) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: " + std::to_string(n_keys) + " ids for the stream's " + std::to_string(total_comp) + " components");
+	if (uniq.empty() || uniq.back() > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: component ids must lie in 0 .. 2^32 - 1");
+	if (key_width != byte_width(uniq.size())) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: key width does not match the number of values");
+	const int sw = h.stored_data_width;
+	const uint64_t cwb = static_cast<uint64_t>(byte_width(static_cast<uint64_t>(h.sx) * h.sy)) * h.sz;
+	h.num_label_bytes = 8 + uniq.size() * sw + cwb + total_comp * key_width;
+	// header | z-index + crc | labels | model | crack codes | labels crc | slice crcs
+	const uint64_t gib = h0.grid_index_bytes(), tail = 4ull * (static_cast<uint64_t>(h0.sz) + 1);
+	const uint64_t body0 = h0.header_bytes() + gib + h0.num_label_bytes;      // model + crack codes: up to the crc tail
+	const uint64_t body = n - tail - body0;
+	const uint64_t len = Header::kBytes + gib + h.num_label_bytes + body + tail;
+	uint8_t* o = static_cast<uint8_t*>(malloc(len));
+	if (!o) throw Error(CKL_ERR_RUNTIME, "crackle_amd: out of host memory");
+	h.write(hb);
+	memcpy(o, hb.data(), hb.size());
+	uint64_t at = hb.size();
+	auto put = [&](uint64_t v, int w) { for (int b = 0; b < w; b++) o[at++] = static_cast<uint8_t>((v >> (8 * b)) & 0xFF); };
+	memcpy(o + at, buf + h0.header_bytes(), gib); at += gib;
+	const uint64_t lab0 = at;
+	put(uniq.size(), 8);
+	for (uint64_t v : uniq) put(v, sw);
+	memcpy(o + at, counts, cwb); at += cwb;
+	memcpy(o + at, keys, total_comp * key_width); at += total_comp * key_width;
+	memcpy(o + at, buf + body0, body); at += body;
+	put(crc32c(o + lab0, h.num_label_bytes), 4);
+	memcpy(o + at, buf + n - 4ull * h0.sz, 4ull * h0.sz); at += 4ull * h0.sz;
+	*out_len = at;
+	return o;
+}
+
+}  // namespace ckl
+
+extern "C" int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint64_t* new_ids, uint64_t n_ids, uint8_t** out, uint64_t* out_len) {
+	try {
+		if (!buf || !out || !out_len || (!new_ids && n_ids)) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*out = nullptr; *out_len = 0;
+		std::vector<uint64_t> uniq(new_ids, new_ids + n_ids);
+		std::sort(uniq.begin(), uniq.end());
+		uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+		const int kw = byte_width(uniq.size());
+		std::vector<uint8_t> keys;
+		keys.reserve(n_ids * kw);
+		// ids are mostly 0 .. N: a direct table where they are dense, a search where they are not
+		const bool dense = !uniq.empty() && uniq.back() < 2 * uniq.size() + 16;
+		std::vector<uint32_t> index;
+		if (dense) {
+			index.resize(uniq.back() + 1);
+			for (size_t i = 0; i < uniq.size(); i++) index[uniq[i]] = static_cast<uint32_t>(i);
+		}
+		for (uint64_t i = 0; i < n_ids; i++) {
+			const uint64_t k = dense ? index[new_ids[i]] : static_cast<uint64_t>(std::lower_bound(uniq.begin(), uniq.end(), new_ids[i]) - uniq.begin());
+			put_le(keys, k, kw);
+		}
+		*out = relabel_stream(buf, n, uniq, keys.data(), kw, n_ids, out_len);
+		return CKL_OK;
+	}
+	catch (const Error& e) { set_last_error(e.what()); return e.status; }
+	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+}

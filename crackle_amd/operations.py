@@ -1,7 +1,7 @@
 """Stream surgery on .ckl bytes without decoding — the slab merge the sharded encoder is built
 on, exposed with the reference's names (crackle/operations.py:424-662: zstack, zsplit,
 zshatter).  Host only (native: ckl_zstack / ckl_zsplit); FLAT label streams.  The consumers
-array_equal, mode_pooling_2x2x1, point_cloud and contacts run on the device."""
+array_equal, mode_pooling_2x2x1, point_cloud, contacts and connected_components run on the device."""
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -236,3 +236,80 @@ def contacts(
   for (a, b), (nx, ny, nz) in zip(pairs.tolist(), faces.tolist()):
     out[(a, b)] = float(np.float32(nx * ax + ny * ay + nz * az))
   return out
+
+
+def relabel_components(binary: bytes, new_ids) -> bytes:
+  """The stream with 2D component i of its slices (stream order) given the value new_ids[i]: uint32,
+  FLAT labels, everything but header and label section copied (ckl_relabel_components; host only)."""
+  b = bytes(binary)
+  ids = np.ascontiguousarray(new_ids, dtype=np.uint64)
+  out, n = C.c_void_p(), C.c_uint64()
+  if _lib.lib().ckl_relabel_components(b, len(b), ids.ctypes.data, ids.size, C.byref(out), C.byref(n)) != _lib.CKL_OK:
+    raise ValueError(_lib.last_error())
+  return _take(out, n)
+
+
+def connected_components(
+  binary: bytes, connectivity: int = 26, binary_image: bool = False,
+  memory_target: int = int(100e6), progress: bool = False,
+  return_mapping: bool = False, device: int = 0,
+) -> Union[bytes, Tuple[bytes, Dict[int, int]]]:
+  """3D connected component labelling of a stream, as a new stream (crackle/operations.py:859-934,
+  which needs the cc3d package; like it this returns bytes, whatever its docstring says).
+
+  Every voxel whose label is not 0 is foreground (negative labels too); label 0 stays 0.  Two
+  foreground voxels are in one component when a chain of voxels with the SAME LABEL joins them by
+  6-, 18- or 26-neighbour steps (`connectivity`).  With return_mapping: also {component id:
+  original label}, labels as crackle_amd.labels(binary) reports them.
+
+  Numbering is this project's own definition: components are numbered 1 .. N in the order of their
+  first voxel, x fastest, then y, then z, in array indices, whatever the stream's fortran_order
+  flag.  (cc3d.connected_components is expected to give the same order for a Fortran-ordered volume;
+  that package was not at hand to check.)
+
+  Nothing is decoded to voxels.  The crack codes already hold the 4-connected components of every
+  slice, and in-plane neighbours with one label are one such component, so no crack changes: the
+  device links the 2D components across rows, diagonals and slices (ckl_connected_components) and
+  only header and label section are written anew; z-index, markov model, crack codes and slice crcs
+  are the input's bytes.  The output is uint32 with FLAT labels, format version 1.  It equals
+  compress(result.astype(uint32), markov_model_order=m) byte for byte when the input came from
+  compress() with markov order m and the encoder picks the same crack_format for the relabelled
+  volume.  The encoder takes that format from pixel_pairs < voxels / 2 (src/crackle.hpp:48-55);
+  relabelling can only lower pixel_pairs, at row and slice wrap-arounds, so only a volume sitting on
+  that threshold comes out with the other format.  This function always keeps the input's.
+
+  memory_target and progress are accepted for the reference's signature and ignored: there are no
+  slabs.  binary_image=True (all nonzero voxels one foreground) merges different labels, which
+  removes cracks and needs a re-encode: ValueError.  Format version 0 streams carry no crack crcs:
+  ValueError.  FLAT and pin label streams are accepted."""
+  if connectivity not in (6, 18, 26):
+    raise ValueError(f"connected_components: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  if binary_image:
+    raise ValueError(
+      "connected_components: binary_image=True is not supported: merging different labels removes "
+      "cracks, which needs a re-encode of the crack codes.")
+  b = bytes(binary)
+  head = header(b)
+  if head.format_version == 0:
+    raise ValueError("connected_components: format version 0 streams have no crack crcs to carry over; re-compress first.")
+  L = _lib.lib()
+  out, n, lab, cnt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+  rc = L.ckl_connected_components(b, len(b), int(connectivity), int(device), C.byref(out), C.byref(n),
+                                  C.byref(lab) if return_mapping else None, C.byref(cnt))
+  if rc != _lib.CKL_OK:
+    if rc == _lib.CKL_ERR_ARG:
+      raise ValueError(_lib.last_error())
+    raise RuntimeError(_lib.last_error())
+  try:
+    result = C.string_at(out.value, n.value)
+    if not return_mapping:
+      return result
+    k = int(cnt.value)
+    orig = np.ctypeslib.as_array(C.cast(lab, C.POINTER(C.c_uint64)), shape=(k,)).copy() if k else np.zeros(0, np.uint64)
+    if head.signed:
+      orig = orig.view(np.int64)
+    return result, {i + 1: v for i, v in enumerate(orig.tolist())}
+  finally:
+    L.ckl_free(out)
+    if lab.value:
+      L.ckl_free(lab)

@@ -419,6 +419,28 @@ int ckl_reencode_markov(const uint8_t* buf, uint64_t n, int markov_model_order, 
  * *out is released with ckl_free. */
 int ckl_zsplit(const uint8_t* buf, uint64_t n, int64_t z_start, int64_t z_end, uint8_t** out, uint64_t* out_len);
 
+/* Replaces crackle.operations.connected_components (crackle/operations.py:859-934, which decodes
+ * slabs, calls the cc3d package and compresses again): the stream in which every 3D-connected piece
+ * of a label has an id of its own, 1 .. N in the order of the pieces' first voxels (x fastest, then
+ * y, then z); label 0 stays 0.  connectivity is 6, 18 or 26.  The crack codes already hold the
+ * 4-connected components of every slice, so the device only links those across rows, diagonals and
+ * slices (k_run_links: a union-find over the components) and numbers the sets; z-index, markov
+ * model, crack codes and slice crcs are copied, header and label section (uint32, FLAT) are new.
+ * component_labels (optional): the original label of component i + 1, as ckl_decoder_label_stats
+ * reports labels (sign-extended); n_components (optional): N.  Version 0 streams are refused
+ * (CKL_ERR_ARG).  Release *out and *component_labels with ckl_free. */
+int ckl_connected_components(
+	const uint8_t* buf, uint64_t n, int connectivity, int device,
+	uint8_t** out, uint64_t* out_len, uint64_t** component_labels, uint64_t* n_components);
+
+/* The stream `buf` (version 1, FLAT or pin labels) with 2D component i of its slices, in stream order,
+ * given the value new_ids[i] (0 .. 2^32 - 1; n_ids must be the stream's component count): data width
+ * 4, unsigned, FLAT labels written as labels::encode_flat does (src/labels.hpp:92-155), stored width
+ * and key width from the values, everything else copied.  Host only, no device needed: the assembly
+ * step of ckl_connected_components, exported so that it can be tested on its own.  *out is released
+ * with ckl_free. */
+int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint64_t* new_ids, uint64_t n_ids, uint8_t** out, uint64_t* out_len);
+
 /* crc32c (Castagnoli; src/crc.hpp:51-57) of a host buffer — exported for tests. */
 uint32_t ckl_crc32c(const uint8_t* data, uint64_t n);
 /* crc32c(A || B) from crc32c(A), crc32c(B) and the byte length of B: lets the ranks of a sharded

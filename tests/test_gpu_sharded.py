@@ -55,6 +55,13 @@ def _volume(kind):
   if kind == "c4":
     # C4's slice shape: 2048 x 2048 (x_width = y_width = 2, component_width = 4)
     return synth.as_numpy_f(synth.voronoi_labels((2048, 2048, 4), np.uint32, seed=45, cell=(32, 32, 8), device=dev))
+  if kind in ("pairs_at_half", "pairs_below_half"):
+    # exactly H = voxels // 2 equal linear neighbours (the first IMPERMISSIBLE count) and H - 1: the stretch of equal
+    # voxels ends the volume and, at H, begins with the first slab's last voxel, so the pair that straddles the slabs
+    # is one of the H (tests/test_threshold_volumes_cpu.py)
+    import threshold_volumes
+    h = 64 * 33 * 4 // 2
+    return threshold_volumes.sharded_volume(h if kind == "pairs_at_half" else h - 1)
   raise ValueError(kind)
 
 
@@ -69,6 +76,8 @@ CASES = [
   # ... unless asked for, or when the chosen pins' id lists pass their budget (here: one entry)
   ("voronoi", 5, True, "CKL_PINS_ON_ROOT"), ("voronoi", 0, True, "CKL_PIN_IDS_BUDGET"),
   ("pin_counts", 0, True, None), ("pin_counts", 0, True, "CKL_TEST_NO_COLLECT"),
+  # the crack format on either side of pixel_pairs = voxels // 2, the deciding pair across the slab boundary
+  ("pairs_at_half", 0, False, None), ("pairs_below_half", 0, False, None), ("pairs_at_half", 0, True, None),
 ]
 ENVS = ("CKL_SHARDED_LEGACY", "CKL_TEST_MERGE_FAIL", "CKL_TEST_NO_COLLECT", "CKL_PINS_ON_ROOT", "CKL_PIN_IDS_BUDGET")
 
@@ -150,6 +159,9 @@ def test_sharded_hip_backend_equals_whole_volume(checker, sharded_results, index
     import crackle_amd
     whole = crackle_amd.compress(vol, allow_pins=True)
     assert np.array_equal(checker.decompress(whole).reshape(vol.shape, order="F"), vol)
+  if kind.startswith("pairs_"):
+    import crackle_amd
+    assert crackle_amd.header(whole).crack_format == (0 if kind == "pairs_at_half" else 1), "the volume left the threshold"
   assert sharded_results[(0, index)][0] == whole, "merged slab streams differ from the whole-volume stream"
   assert sharded_results[(1, index)][0] is None
   assert sharded_results[(0, index)][1] and sharded_results[(1, index)][1], "a rank decoded its z-range wrongly"

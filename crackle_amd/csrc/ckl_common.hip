@@ -414,7 +414,7 @@ int ckl_device_count(void) {
 }
 
 int ckl_header_info_from_bytes(const uint8_t* buf, uint64_t n, ckl_header_info* out) {
-	try {
+	return guard([&] {
 		if (!buf || !out) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		Header h = Header::parse(buf, n);
 		out->format_version = h.format_version;
@@ -429,10 +429,7 @@ int ckl_header_info_from_bytes(const uint8_t* buf, uint64_t n, ckl_header_info* 
 		out->is_sorted = h.is_sorted;
 		out->num_label_bytes = h.num_label_bytes;
 		out->header_bytes = h.header_bytes();
-		return CKL_OK;
-	}
-	catch (const Error& e) { set_last_error(e.what()); return e.status; }
-	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 void ckl_free(void* p) { host_out_free(p); }

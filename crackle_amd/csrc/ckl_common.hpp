@@ -9,8 +9,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/crackle_amd.h"
@@ -164,6 +166,38 @@ struct DevBuf {
 
 void set_last_error(const std::string& msg);
 int select_device(int device);   // throws CKL_ERR_NO_DEVICE
+
+// The body of a C entry point: what it throws becomes the last error and a status.  A body returns
+// nothing (CKL_OK) or a status, e.g. the one another entry point gave it, whose last-error text then
+// stands.  What a body owns it holds in the owners below: nothing is cleaned up here.
+template <class F>
+int guard(F&& body) {
+	try {
+		if constexpr (std::is_void<decltype(body())>::value) { body(); return CKL_OK; }
+		else return body();
+	}
+	catch (const Error& e) { set_last_error(e.what()); return e.status; }
+	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+}
+
+struct SessionDeleter {
+	void operator()(ckl_decoder* d) const { ckl_decoder_destroy(d); }
+	void operator()(ckl_encoder* e) const { ckl_encoder_destroy(e); }
+};
+typedef std::unique_ptr<ckl_decoder, SessionDeleter> DecoderPtr;
+typedef std::unique_ptr<ckl_encoder, SessionDeleter> EncoderPtr;
+// ckl_decoder_create into an owner; the status (and the last error) are ckl_decoder_create's
+inline int open_decoder(const uint8_t* buf, uint64_t n, int64_t z_start, int64_t z_end, int device, DecoderPtr& d) {
+	ckl_decoder* raw = nullptr;
+	const int rc = ckl_decoder_create(buf, n, z_start, z_end, device, &raw);
+	d.reset(raw);
+	return rc;
+}
+
+// a result block of host_out_alloc until the caller has it: release() on the success path
+struct HostFree { void operator()(void* p) const { host_out_free(p); } };
+template <typename T> using HostOut = std::unique_ptr<T[], HostFree>;
+template <typename T> HostOut<T> host_out(size_t count) { return HostOut<T>(static_cast<T*>(host_out_alloc(count * sizeof(T)))); }
 // Orders `s` after everything already submitted to the device's default (null) stream:
 // the sessions run on their own non-blocking streams, and callers such as PyTorch fill /
 // clear the buffers they hand over on the default stream.

@@ -1,5 +1,5 @@
 // 3D connected components from the run tables: the device half of connected_components.
-// (Included by ckl_decode.hip inside namespace ckl, after the contacts kernels whose run walk and
+// (Included by ckl_operations.hip inside namespace ckl, after the contacts kernels whose run walk and
 // constants it shares: kContactBlock / kContactPer / kContactRuns, kNoKey.)
 //
 // The crack codes of a slice already describe its 4-connected components, and the decoder numbers

@@ -21,7 +21,7 @@
 //                      (operations.hpp:229-257)
 #pragma once
 #include "ckl_device.hpp"
-#include "ckl_runs.hpp"
+#include "ckl_run_types.hpp"
 
 namespace ckl {
 namespace dev {

@@ -2838,7 +2838,7 @@ void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_sign
 extern "C" {
 
 int ckl_encoder_create(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int device, ckl_encoder** out) {
-	try {
+	return guard([&] {
 		if (!out) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		check_dims(sx, sy, sz, dtype_bytes, 0);
 		select_device(device);
@@ -2862,10 +2862,7 @@ int ckl_encoder_create(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int 
 		CKL_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
 		CKL_HIP(hipEventCreateWithFlags(&e->ev_prezero, hipEventDisableTiming));
 		*out = e.release();
-		return CKL_OK;
-	}
-	catch (const Error& e) { set_last_error(e.what()); return e.status; }
-	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_run(
@@ -2874,7 +2871,7 @@ int ckl_encoder_run(
 	int optimize_pins, int auto_bgcolor, int64_t manual_bgcolor,
 	const ckl_encode_overrides* overrides, uint8_t** out, uint64_t* out_len
 ) {
-	try {
+	return guard([&] {
 		if (!e || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		check_dims(sx, sy, sz, e->dtype_bytes, 0);
 		if (markov_model_order > 15) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [0, 15]");
@@ -2896,21 +2893,15 @@ int ckl_encoder_run(
 		if (getenv("CKL_PROFILE")) {
 			fprintf(stderr, "[ckl encoder_run ms] encode=%.2f\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run0).count());
 		}
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_reencode_markov(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
-	try {
+	return guard([&] {
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		select_device(device);
 		reencode_markov(buf, n, markov_model_order, device, out, out_len);
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_defer_codes(ckl_encoder* e, int defer) {
@@ -2926,17 +2917,14 @@ int ckl_encoder_async_host_copy(ckl_encoder* e, int on) {
 }
 
 int ckl_encoder_host_wait(ckl_encoder* e) {
-	try {
+	return guard([&] {
 		if (!e) throw Error(CKL_ERR_ARG, "crackle_amd: null encoder");
 		if (e->host_copy_pending) {
 			select_device(e->device);
 			CKL_HIP(hipStreamSynchronize(e->stream_copy));
 			e->host_copy_pending = false;
 		}
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_keep_device_stream(ckl_encoder* e, int keep) {
@@ -2954,10 +2942,10 @@ int ckl_encoder_device_stream(const ckl_encoder* e, const uint8_t** stream_devic
 }
 
 int ckl_encoder_codes_to_host(ckl_encoder* e, uint8_t* dst_host, uint64_t capacity, uint64_t* n_bytes) {
-	try {
+	return guard([&] {
 		if (!e || !n_bytes) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		*n_bytes = e->last_codes_total;
-		if (e->last_codes_total == 0) return CKL_OK;
+		if (e->last_codes_total == 0) return;
 		if (!dst_host || capacity < e->last_codes_total) throw Error(CKL_ERR_ARG, "crackle_amd: code buffer too small: need " + std::to_string(e->last_codes_total) + " bytes");
 		select_device(e->device);
 		if (e->async_host_copy) {
@@ -2965,21 +2953,18 @@ int ckl_encoder_codes_to_host(ckl_encoder* e, uint8_t* dst_host, uint64_t capaci
 			if (!e->stream_copy) CKL_HIP(hipStreamCreateWithFlags(&e->stream_copy, hipStreamNonBlocking));
 			CKL_HIP(hipMemcpyAsync(dst_host, e->d_codes_out.p, e->last_codes_total, hipMemcpyDeviceToHost, e->stream_copy));
 			e->host_copy_pending = true;
-			return CKL_OK;
+			return;
 		}
 		CKL_HIP(hipMemcpyAsync(dst_host, e->d_codes_out.p, e->last_codes_total, hipMemcpyDeviceToHost, e->stream));
 		CKL_HIP(hipStreamSynchronize(e->stream));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_stats(
 	ckl_encoder* e, const void* labels_device, int64_t sx, int64_t sy, int64_t sz,
 	uint64_t* max_label, uint64_t* pixel_pairs, uint64_t* first_voxel, uint64_t* last_voxel
 ) {
-	try {
+	return guard([&] {
 		if (!e) throw Error(CKL_ERR_ARG, "crackle_amd: null encoder");
 		check_dims(sx, sy, sz, e->dtype_bytes, 0);
 		select_device(e->device);
@@ -3013,17 +2998,14 @@ int ckl_encoder_stats(
 		if (pixel_pairs) *pixel_pairs = st.pairs;
 		if (first_voxel) *first_voxel = st.first;
 		if (last_voxel) *last_voxel = st.last;
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_markov_stats(
 	ckl_encoder* e, const void* labels_device, int64_t sx, int64_t sy, int64_t sz,
 	int crack_format, uint64_t markov_model_order, uint32_t* hist
 ) {
-	try {
+	return guard([&] {
 		if (!e || !hist) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		check_dims(sx, sy, sz, e->dtype_bytes, 0);
 		if (markov_model_order == 0 || markov_model_order > 13) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [1, 13]");
@@ -3047,10 +3029,7 @@ int ckl_encoder_markov_stats(
 			if (cached) { e->trail_for = labels_device; e->trail_perm = perm; e->trail_order = order; }      // (only beside cached planes: the run checks both)
 		}
 		memcpy(hist, h.data(), h.size() * sizeof(uint32_t));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 // shared by ckl_encoder_components / ckl_encoder_components_device: components of the slab, ids
@@ -3086,30 +3065,24 @@ int ckl_encoder_components(
 	ckl_encoder* e, const void* labels_device, int64_t sx, int64_t sy, int64_t sz,
 	uint32_t id_base, uint32_t* cc_host, uint32_t* ncomp_host
 ) {
-	try {
+	return guard([&] {
 		if (!e || !cc_host || !ncomp_host) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		const uint32_t* cc = encoder_components(e, labels_device, sx, sy, sz, id_base, nullptr, ncomp_host);
 		const uint64_t voxels = static_cast<uint64_t>(sx) * sy * sz;
 		if (voxels) CKL_HIP(hipMemcpyAsync(cc_host, cc, voxels * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream2));
 		CKL_HIP(hipStreamSynchronize(e->stream2));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_components_device(
 	ckl_encoder* e, const void* labels_device, int64_t sx, int64_t sy, int64_t sz,
 	uint32_t id_base, uint32_t* cc_device, uint32_t* ncomp_host
 ) {
-	try {
+	return guard([&] {
 		if (!e || !cc_device || !ncomp_host) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		encoder_components(e, labels_device, sx, sy, sz, id_base, cc_device, ncomp_host);
 		CKL_HIP(hipStreamSynchronize(e->stream2));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_pin_labels(
@@ -3118,7 +3091,7 @@ int ckl_encoder_pin_labels(
 	int stored_width, int auto_bgcolor, int64_t manual_bgcolor,
 	uint8_t** out, uint64_t* out_len
 ) {
-	try {
+	return guard([&] {
 		if (!e || !labels_device || !cc_device || !ncomp_host || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (sx <= 0 || sy <= 0 || sz <= 0) throw Error(CKL_ERR_ARG, "crackle_amd: empty volume");
 		if (sx > 0xFFFFFFFFll || sy > 0xFFFFFFFFll || sz > 0xFFFFFFFFll) throw Error(CKL_ERR_ARG, "crackle_amd: dimensions must fit 32 bits");
@@ -3155,10 +3128,7 @@ int ckl_encoder_pin_labels(
 		memcpy(p, bin.data(), bin.size());
 		*out = p;
 		*out_len = bin.size();
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 
@@ -3179,50 +3149,41 @@ static void pins_rows_check(const ckl_encoder* e, const void* labels, const uint
 
 int ckl_pins_rows_first(ckl_encoder* e, const void* labels_rows, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
 	uint64_t* first_any, uint64_t* first_kept, uint64_t* comp_label) {
-	try {
+	return guard([&] {
 		pins_rows_check(e, labels_rows, cc_rows, sx, rows, sz, y0, n_components);
 		if (!first_any || !first_kept || !comp_label) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		select_device(e->device);
 		wait_for_default_stream(e->stream2, e->ev_in);
 		CKL_ROWS_DISPATCH(pins_rows_first<T>(*e, static_cast<const T*>(labels_rows), cc_rows, sx, rows, sz, y0, n_components, first_any, first_kept, comp_label));
 		CKL_HIP(hipStreamSynchronize(e->stream2));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_pins_rows_best(ckl_encoder* e, const void* labels_rows, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
 	const uint64_t* first_kept, uint64_t* best) {
-	try {
+	return guard([&] {
 		pins_rows_check(e, labels_rows, cc_rows, sx, rows, sz, y0, n_components);
 		if (!first_kept || !best) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		select_device(e->device);
 		wait_for_default_stream(e->stream2, e->ev_in);
 		CKL_ROWS_DISPATCH(pins_rows_best<T>(*e, static_cast<const T*>(labels_rows), cc_rows, sx, rows, sz, y0, n_components, first_kept, best));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_pins_rows_extent(ckl_encoder* e, const void* labels_rows, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
 	const uint64_t* first_kept, const uint64_t* best, uint64_t* choice, uint32_t* ze_plus1) {
-	try {
+	return guard([&] {
 		pins_rows_check(e, labels_rows, cc_rows, sx, rows, sz, y0, n_components);
 		if (!first_kept || !best || !choice || !ze_plus1) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		select_device(e->device);
 		wait_for_default_stream(e->stream2, e->ev_in);
 		CKL_ROWS_DISPATCH(pins_rows_extent<T>(*e, static_cast<const T*>(labels_rows), cc_rows, sx, rows, sz, y0, n_components, first_kept, best, choice, ze_plus1));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_pins_rows_ids(ckl_encoder* e, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
 	const uint64_t* choice, const uint32_t* ze_plus1, const uint64_t* offsets, uint32_t* ids) {
-	try {
+	return guard([&] {
 		if (!e || !cc_rows || !choice || !ze_plus1 || !offsets || !ids) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (sx <= 0 || rows <= 0 || sz <= 0 || y0 < 0 || n_components == 0 || n_components >= kPinNone) throw Error(CKL_ERR_ARG, "crackle_amd: row slab out of range");
 		select_device(e->device);
@@ -3238,16 +3199,13 @@ int ckl_pins_rows_ids(ckl_encoder* e, const uint32_t* cc_rows, int64_t sx, int64
 		hipLaunchKernelGGL(k_pin_minus1, dim3(nb), dim3(kPinBlock), 0, s, ze_plus1, n_components, d_ze.p);
 		hipLaunchKernelGGL(k_pin_ids, dim3(nb), dim3(kPinBlock), 0, s, v, reinterpret_cast<const unsigned long long*>(choice), d_ze.p, offsets, static_cast<uint32_t>(n_components), ids);
 		CKL_HIP(hipStreamSynchronize(s));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_pins_rows_section(ckl_encoder* e, int64_t sx, int64_t sy, int64_t sz, uint64_t n_components, const uint32_t* ncomp_host,
 	const uint64_t* comp_label, const uint64_t* first_any, const uint64_t* choice, const uint32_t* ze_plus1, const uint64_t* offsets, const uint32_t* ids,
 	int stored_width, int auto_bgcolor, int64_t manual_bgcolor, uint8_t** out, uint64_t* out_len) {
-	try {
+	return guard([&] {
 		if (!e || !ncomp_host || !comp_label || !first_any || !choice || !ze_plus1 || !offsets || !ids || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (sx <= 0 || sy <= 0 || sz <= 0) throw Error(CKL_ERR_ARG, "crackle_amd: empty volume");
 		if (stored_width != 1 && stored_width != 2 && stored_width != 4 && stored_width != 8) throw Error(CKL_ERR_ARG, "crackle_amd: stored width must be 1, 2, 4 or 8 bytes");
@@ -3264,10 +3222,7 @@ int ckl_pins_rows_section(ckl_encoder* e, int64_t sx, int64_t sy, int64_t sz, ui
 		memcpy(p, bin.data(), bin.size());
 		*out = p;
 		*out_len = bin.size();
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 int ckl_encoder_last_timing(const ckl_encoder* e, float* pipeline_ms, float* dominant_kernel_ms) {
@@ -3278,7 +3233,7 @@ int ckl_encoder_last_timing(const ckl_encoder* e, float* pipeline_ms, float* dom
 }
 
 int ckl_encoder_walk_paths(ckl_encoder* e, uint32_t* fast_slices, uint32_t* compiled_slices) {
-	try {
+	return guard([&] {
 		if (!e) throw Error(CKL_ERR_ARG, "crackle_amd: null encoder");
 		uint32_t fast = 0, plain = 0;
 		const size_t ns = e->last_trail_slices;
@@ -3290,10 +3245,7 @@ int ckl_encoder_walk_paths(ckl_encoder* e, uint32_t* fast_slices, uint32_t* comp
 		}
 		if (fast_slices) *fast_slices = fast;
 		if (compiled_slices) *compiled_slices = plain;
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 // grid = slices, block = kBlock: the walk's events of a slice by kind, and the longest run of events that take no decision
@@ -3319,11 +3271,11 @@ __global__ void __launch_bounds__(kBlock) k_trail_step_kinds(const uint32_t* __r
 }
 
 int ckl_encoder_walk_step_kinds(ckl_encoder* e, uint32_t* counts, uint32_t max_slices, uint32_t* n_slices) {
-	try {
+	return guard([&] {
 		if (!e || !counts || !n_slices) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		const size_t ns = e->last_trail_slices;
 		*n_slices = static_cast<uint32_t>(ns);
-		if (!ns || !e->t_counters.p || !e->t_events.p) { *n_slices = 0; return CKL_OK; }
+		if (!ns || !e->t_counters.p || !e->t_events.p) { *n_slices = 0; return; }
 		if (ns > max_slices) throw Error(CKL_ERR_ARG, "crackle_amd: counts holds fewer slices than the last run had");
 		select_device(e->device);
 		DevBuf<uint32_t> d_counts;
@@ -3331,10 +3283,7 @@ int ckl_encoder_walk_step_kinds(ckl_encoder* e, uint32_t* counts, uint32_t max_s
 		hipLaunchKernelGGL(k_trail_step_kinds, dim3(static_cast<uint32_t>(ns)), dim3(kBlock), 0, e->stream, e->t_events.p, e->t_ibase.p, e->t_counters.p + 5 * ns, d_counts.p);
 		CKL_HIP(hipMemcpyAsync(counts, d_counts.p, ns * 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
 		CKL_HIP(hipStreamSynchronize(e->stream));
-		return CKL_OK;
-	}
-	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 void ckl_encoder_destroy(ckl_encoder* e) { delete e; }
@@ -3371,9 +3320,10 @@ int ckl_compress(
 		}
 	}
 	catch (const Error& err) { set_last_error(err.what()); return err.status; }
-	int rc = ckl_encoder_create(sx, sy, sz, dtype_bytes, device, &e);
+	const int rc = ckl_encoder_create(sx, sy, sz, dtype_bytes, device, &e);
 	if (rc != CKL_OK) return rc;
-	try {
+	const EncoderPtr owner(e);
+	return guard([&]() -> int {
 		const uint64_t bytes = static_cast<uint64_t>(sx) * sy * sz * dtype_bytes;
 		const void* dev_labels = labels;
 		DevBuf<uint8_t> tmp;
@@ -3383,13 +3333,9 @@ int ckl_compress(
 			CKL_HIP(hipMemcpy(tmp.p, labels, bytes, hipMemcpyHostToDevice));
 			dev_labels = tmp.p;
 		}
-		rc = ckl_encoder_run(e, dev_labels, sx, sy, sz, allow_pins, fortran_order, markov_model_order,
+		return ckl_encoder_run(e, dev_labels, sx, sy, sz, allow_pins, fortran_order, markov_model_order,
 			optimize_pins, auto_bgcolor, manual_bgcolor, nullptr, out, out_len);
-		ckl_encoder_destroy(e);
-		return rc;
-	}
-	catch (const Error& err) { set_last_error(err.what()); ckl_encoder_destroy(e); return err.status; }
-	catch (const std::exception& err) { set_last_error(err.what()); ckl_encoder_destroy(e); return CKL_ERR_RUNTIME; }
+	});
 }
 
 }  // extern "C"

@@ -674,7 +674,7 @@ extern "C" int ckl_pin_labels_host(
 	uint8_t** out, uint64_t* out_len
 ) {
 	using namespace ckl;
-	try {
+	return guard([&] {
 		if (!labels || !cc || !ncomp || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (sx <= 0 || sy <= 0 || sz <= 0) throw Error(CKL_ERR_ARG, "crackle_amd: empty volume");
 		if (stored_width != 1 && stored_width != 2 && stored_width != 4 && stored_width != 8) throw Error(CKL_ERR_ARG, "crackle_amd: stored width must be 1, 2, 4 or 8 bytes");
@@ -695,8 +695,5 @@ extern "C" int ckl_pin_labels_host(
 		memcpy(p, bin.data(), bin.size());
 		*out = p;
 		*out_len = bin.size();
-		return CKL_OK;
-	}
-	catch (const Error& e) { set_last_error(e.what()); return e.status; }
-	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+	});
 }

@@ -69,7 +69,7 @@ Slab parse_slab(const uint8_t* buf, uint64_t n) {
 }  // namespace
 
 extern "C" int ckl_zstack(const uint8_t* const* bufs, const uint64_t* lens, uint64_t count, uint8_t** out, uint64_t* out_len) {
-	try {
+	return guard([&] {
 		if (!bufs || !lens || !out || !out_len || count == 0) throw Error(CKL_ERR_ARG, "crackle_amd: zstack needs at least one stream");
 		std::vector<Slab> slabs;
 		slabs.reserve(count);
@@ -138,10 +138,7 @@ extern "C" int ckl_zstack(const uint8_t* const* bufs, const uint64_t* lens, uint
 		memcpy(p, bin.data(), bin.size());
 		*out = p;
 		*out_len = bin.size();
-		return CKL_OK;
-	}
-	catch (const Error& e) { set_last_error(e.what()); return e.status; }
-	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 // Native form of crackle.operations.zsplit's helper (crackle/operations.py:550-623): the stream
@@ -150,7 +147,7 @@ extern "C" int ckl_zstack(const uint8_t* const* bufs, const uint64_t* lens, uint
 // keys re-keyed, stored width = byte width of the largest label left.  Unlike the reference's
 // helper the markov model is carried along, so streams with a model stay decodable.
 extern "C" int ckl_zsplit(const uint8_t* buf, uint64_t n, int64_t z_start, int64_t z_end, uint8_t** out, uint64_t* out_len) {
-	try {
+	return guard([&] {
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		const Slab s = parse_slab(buf, n);
 		const Header& h0 = s.h;
@@ -205,10 +202,7 @@ extern "C" int ckl_zsplit(const uint8_t* buf, uint64_t n, int64_t z_start, int64
 		memcpy(o + at, s.crcs + 4 * z_start, 4 * nsl); at += 4 * nsl;
 		*out = o;
 		*out_len = at;
-		return CKL_OK;
-	}
-	catch (const Error& e) { set_last_error(e.what()); return e.status; }
-	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+	});
 }
 
 // ------------------------------------------------------------------------------
@@ -304,7 +298,7 @@ uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64
 }  // namespace ckl
 
 extern "C" int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint64_t* new_ids, uint64_t n_ids, uint8_t** out, uint64_t* out_len) {
-	try {
+	return guard([&] {
 		if (!buf || !out || !out_len || (!new_ids && n_ids)) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		*out = nullptr; *out_len = 0;
 		std::vector<uint64_t> uniq(new_ids, new_ids + n_ids);
@@ -325,8 +319,5 @@ extern "C" int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint
 			put_le(keys, k, kw);
 		}
 		*out = relabel_stream(buf, n, uniq, keys.data(), kw, n_ids, out_len);
-		return CKL_OK;
-	}
-	catch (const Error& e) { set_last_error(e.what()); return e.status; }
-	catch (const std::exception& e) { set_last_error(e.what()); return CKL_ERR_RUNTIME; }
+	});
 }

@@ -46,7 +46,7 @@ def _max_grid():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# restated host rules (ckl_decode.hip: decoder_point_cloud, decoder_label_stats)
+# restated host rules (ckl_operations.hip: decoder_point_cloud, decoder_label_stats)
 def pc_lds_visited(sx, sy):
   """The tracer keeps its visited bits in LDS (else in HBM)."""
   return -(-sx * sy // 32) * 4 + 256 <= _max_lds()

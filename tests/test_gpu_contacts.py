@@ -1,4 +1,4 @@
-"""GPU tests of contacts (crackle_amd/csrc/ckl_decode.hip: k_run_contacts, k_contacts_compact behind
+"""GPU tests of contacts (crackle_amd/csrc/ckl_operations.hip: k_run_contacts, k_contacts_compact behind
 ckl_decoder_contacts) against the reference's recorded output (tests/golden/contacts.json, see
 tests/test_contacts_cpu.py for how it was recorded) and the numpy restatement contacts_numpy, which
 tests/test_contacts_cpu.py pins to that output.  Face counts are compared exactly through

@@ -1651,8 +1651,8 @@ void crack_pass(
 		CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
 		const size_t budget = static_cast<size_t>(max_lds > 1024 ? max_lds - 1024 : 0);
 		const uint32_t dart_blocks = (4 * max_ncap + kWalkChunk * kWaves - 1) / (kWalkChunk * kWaves);
-		// union-find table of k_trail_components in LDS: 4 bytes per node
-		size_t clds = (static_cast<size_t>(max_special) + 1024) * 4;
+		// union-find table (4 bytes per node) and component minima (8) of k_trail_components in LDS
+		size_t clds = (static_cast<size_t>(max_special) + 1024) * 12;
 		if (const char* env = getenv("CKL_TRAIL_LDS")) clds = static_cast<size_t>(std::max(0, atoi(env)));
 		clds = (std::min(budget, std::max<size_t>(clds, 1024)) / 16) * 16;
 		CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trail_components), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(clds)));

@@ -16,7 +16,7 @@
 //                      at the other end: end node, arrival edge, length, smallest vertex
 //   k_trail_loops      closed loops without a node: found from their smallest vertex
 //   k_trail_components one workgroup per slice: components of the node graph (union-find
-//                      in LDS) and their smallest vertex = where next_cluster starts the
+//                      and minima in LDS) and their smallest vertex = where next_cluster starts the
 //                      chain (crackcodes.hpp:41-49, 399); a start in the middle of a
 //                      segment splits it; start vertices in ascending order (bitmap scan)
 //   k_trail_walk       the exact serial trail, but over nodes only (tables in LDS) and reduced to
@@ -593,55 +593,75 @@ __device__ __forceinline__ void tuf_unite(uint32_t* L, uint32_t a, uint32_t b) {
 constexpr uint32_t kStartList = 2048;   // start vertices ranked directly up to this many per slice
 constexpr int kCompBlock = 256;      // threads of k_trail_components (one workgroup per slice)
 
-template <bool LDS>
-__device__ __forceinline__ void trail_components_slice(const TrailArgs& a, uint32_t zi, uint32_t* parent, uint32_t nn, uint32_t* s_scan, uint32_t* s_nstart) {
+// LDS: the union-find table is in LDS; CMLDS: so are the components' minima (else a.parent / a.compmin)
+template <bool LDS, bool CMLDS>
+__device__ __forceinline__ void trail_components_slice(const TrailArgs& a, uint32_t zi, uint32_t* parent, unsigned long long* compmin, uint32_t nn, uint32_t* s_scan, uint32_t* s_nstart) {
 	const uint64_t nb = a.nbase[zi];
 	uint32_t* start_tmp = a.items + a.ibase[zi];      // the item table is not in use yet (capacity >= kStartList)
 	unsigned long long dg_t = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
 	auto stamp = [&](int slot) { if (a.dbg && threadIdx.x == 0) { const unsigned long long now = __builtin_amdgcn_s_memtime(); atomicAdd(a.dbg + slot, now - dg_t); dg_t = now; } };
 	const uint32_t* dart_end = a.dart_end + nb * 4u;
-	unsigned long long* compmin = a.compmin + nb;
-	for (uint32_t j = threadIdx.x; j < nn; j += kCompBlock) { parent[j] = j; compmin[j] = ~0ull; }
+	auto cm_load = [&](uint32_t j) -> unsigned long long {
+		if (CMLDS) return __hip_atomic_load(compmin + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		return __hip_atomic_load(compmin + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	};
+	for (uint32_t j = threadIdx.x; j < nn; j += kCompBlock) parent[j] = j;
 	__syncthreads();
 	if (!LDS) __threadfence();
-	// the dart ends of kUniteBatch steps are loaded before the first union: the unions are dependent
-	// round trips to the table and would otherwise wait for memory once per step
-	constexpr uint32_t kUniteBatch = 8;
-	for (uint32_t d0 = threadIdx.x; d0 < nn * 4u; d0 += kCompBlock * kUniteBatch) {
-		uint32_t e[kUniteBatch];
+	// A thread takes whole nodes: the four dart ends and the four smallest vertices of kNodeBatch nodes are loaded
+	// (16 bytes each) before the first union: the unions are dependent round trips to the table and would otherwise
+	// wait for memory once per step.  The node's own minimum over its (at most four) segments goes to compmin[j]:
+	// the minima phase below starts from there and never goes to the dart arrays again.
+	constexpr uint32_t kNodeBatch = 4;
+	for (uint32_t j0 = threadIdx.x; j0 < nn; j0 += kCompBlock * kNodeBatch) {
+		uint4 e4[kNodeBatch], m4[kNodeBatch];
 #pragma unroll
-		for (uint32_t k = 0; k < kUniteBatch; k++) {
-			const uint32_t d = d0 + k * kCompBlock;
-			e[k] = d < nn * 4u ? dart_end[d] : kDartNone;
+		for (uint32_t k = 0; k < kNodeBatch; k++) {
+			const uint32_t j = j0 + k * kCompBlock;
+			e4[k] = make_uint4(kDartNone, kDartNone, kDartNone, kDartNone);
+			m4[k] = make_uint4(0u, 0u, 0u, 0u);
+			if (j < nn) {
+				e4[k] = *reinterpret_cast<const uint4*>(dart_end + j * 4u);
+				m4[k] = *reinterpret_cast<const uint4*>(a.dart_minv + nb * 4u + j * 4u);
+			}
 		}
 #pragma unroll
-		for (uint32_t k = 0; k < kUniteBatch; k++) {
-			if (e[k] == kDartNone) continue;
-			const uint32_t j = (d0 + k * kCompBlock) >> 2, j2 = e[k] >> 2;
-			if (j < j2 && j2 < nn) tuf_unite<LDS>(parent, j, j2);      // the dart at the far end names the same segment
+		for (uint32_t k = 0; k < kNodeBatch; k++) {
+			const uint32_t j = j0 + k * kCompBlock;
+			if (j >= nn) continue;
+			const uint32_t ee[4] = { e4[k].x, e4[k].y, e4[k].z, e4[k].w }, mm[4] = { m4[k].x, m4[k].y, m4[k].z, m4[k].w };
+			unsigned long long val = ~0ull;
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) {
+				if (ee[q] == kDartNone) continue;
+				const unsigned long long v = (static_cast<unsigned long long>(mm[q]) << 32) | (j * 4u + q);
+				val = v < val ? v : val;
+			}
+			compmin[j] = val;
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) {
+				if (ee[q] == kDartNone) continue;
+				const uint32_t j2 = ee[q] >> 2;
+				if (j < j2 && j2 < nn) tuf_unite<LDS>(parent, j, j2);      // the dart at the far end names the same segment
+			}
 		}
 	}
 	__syncthreads();
-	if (!LDS) __threadfence();
+	if (!LDS || !CMLDS) __threadfence();
 	stamp(12);
-	// smallest vertex of every component and a dart that saw it; lanes of a wavefront that
-	// share a root combine first (a slice usually has one giant component)
+	// smallest vertex of every component and a dart that saw it: every node's own minimum (written above by this
+	// very thread) goes to its root's entry; lanes of a wavefront that share a root combine first (a slice usually
+	// has one giant component).  All unions are done, so only roots' entries are written here, and only they are read below.
 	for (uint32_t j0 = 0; j0 < nn; j0 += kCompBlock) {
 		const uint32_t j = j0 + threadIdx.x;
 		uint32_t root = 0xFFFFFFFFu;
 		unsigned long long val = ~0ull;
 		if (j < nn) {
-			// the node's own minimum over its (at most four) segments first (one 16-byte load each)
-			const uint4 e4 = *reinterpret_cast<const uint4*>(dart_end + j * 4u);
-			const uint4 m4 = *reinterpret_cast<const uint4*>(a.dart_minv + nb * 4u + j * 4u);
-			const uint32_t ee[4] = { e4.x, e4.y, e4.z, e4.w }, mm[4] = { m4.x, m4.y, m4.z, m4.w };
-#pragma unroll
-			for (uint32_t k = 0; k < 4u; k++) {
-				if (ee[k] == kDartNone) continue;
-				const unsigned long long v = (static_cast<unsigned long long>(mm[k]) << 32) | (j * 4u + k);
-				val = v < val ? v : val;
+			val = cm_load(j);
+			if (val != ~0ull) {
+				root = tuf_find<LDS>(parent, j);
+				if (root == j) root = 0xFFFFFFFFu;      // a root's own minimum is in place already
 			}
-			if (val != ~0ull) root = tuf_find<LDS>(parent, j);
 		}
 		unsigned long long todo = __ballot(root != 0xFFFFFFFFu);
 		while (todo) {
@@ -659,32 +679,34 @@ __device__ __forceinline__ void trail_components_slice(const TrailArgs& a, uint3
 		}
 	}
 	__syncthreads();
-	__threadfence();
+	if (!CMLDS) __threadfence();
 	stamp(13);
 	// one thread per component root: mark the start vertex; a start inside a segment
 	// becomes a node of degree 2 (right + down) that splits the segment
 	uint32_t* bits = a.start_bits + static_cast<uint64_t>(zi) * a.start_words;
 	for (uint32_t j = threadIdx.x; j < nn; j += kCompBlock) {
 		if (tuf_load<LDS>(parent, j) != j) continue;
-		const unsigned long long m = __hip_atomic_load(compmin + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const unsigned long long m = cm_load(j);
 		if (m == ~0ull) continue;
 		const uint32_t minv = static_cast<uint32_t>(m >> 32);
 		const uint32_t d = static_cast<uint32_t>(m);
+		// (what the split needs of dart d is asked for in one go, ahead of the atomics)
+		const uint64_t db = nb * 4u;
+		const uint32_t len = a.dart_len[db + d];
+		const uint32_t mp = a.dart_minpos[db + d];
+		const uint32_t d2 = a.dart_end[db + d];              // far end: node << 2 | arrival = the dart that runs back
 		atomicOr(bits + (minv >> 5), 1u << (minv & 31u));
 		{
 			const uint32_t slot = atomicAdd(s_nstart, 1u);
 			if (slot < kStartList) start_tmp[slot] = minv;
 		}
-		const uint64_t db = nb * 4u;
-		const uint32_t len = a.dart_len[db + d];
-		const uint32_t pos = a.dart_minpos[db + d] >> 2, arr = a.dart_minpos[db + d] & 3u;
+		const uint32_t pos = mp >> 2, arr = mp & 3u;
 		if (pos == 0 || pos == len) continue;                // the start is a node (a dead end)
 		const uint32_t s = atomicAdd(a.n_nodes + zi, 1u);
 		if (s >= a.ncap[zi]) { atomicOr(a.slice_err + zi, TRAIL_ERR_CAPACITY); continue; }
 		a.node_vertex[nb + s] = minv;
 		a.node_adj[nb + s] = 5u;
 		a.vert2node[static_cast<uint64_t>(zi) * a.nverts + minv] = s;
-		const uint32_t d2 = a.dart_end[db + d];              // far end: node << 2 | arrival = the dart that runs back
 		const uint32_t other = arr ^ 2u;
 		for (uint32_t q = 0; q < 4; q++) { a.dart_end[db + s * 4u + q] = kDartNone; a.dart_len[db + s * 4u + q] = 0; a.dart_inline[db + s * 4u + q] = 0; }      // (the two halves keep their codes: a prefix)
 		a.dart_end[db + d] = (s << 2) | arr;        a.dart_len[db + d] = pos;
@@ -693,7 +715,9 @@ __device__ __forceinline__ void trail_components_slice(const TrailArgs& a, uint3
 		a.dart_end[db + s * 4u + other] = d2;       a.dart_len[db + s * 4u + other] = len - pos;
 	}
 	__syncthreads();
-	__threadfence();
+	// (the start list and the bitmap go from thread to thread of this workgroup, through the one L1 and L2 they share;
+	// the global path keeps the device-wide fence it always had)
+	if (LDS && CMLDS) __threadfence_block(); else __threadfence();
 	stamp(14);
 	// start vertices in ascending order.  Usually there are a handful: rank them directly;
 	// a slice with many components (noise) scans the bitmap over the vertices instead.
@@ -741,17 +765,19 @@ __device__ __forceinline__ void trail_components_slice(const TrailArgs& a, uint3
 	stamp(15);
 }
 
-// grid = nslices; dynamic LDS = lds_bytes (the union-find table of slices that fit)
+// grid = nslices; dynamic LDS = lds_bytes: the components' minima (8 bytes per node) and the union-find table (4) of
+// slices where both fit, the union-find table alone where only it does; the global arrays otherwise
 static __global__ void __launch_bounds__(kCompBlock) k_trail_components(TrailArgs a, uint32_t lds_bytes) {
-	extern __shared__ uint32_t s_trail[];
+	extern __shared__ unsigned long long s_comp[];
 	__shared__ uint32_t s_scan[kCompBlock / kWave];
 	__shared__ uint32_t s_nstart;
 	const uint32_t zi = blockIdx.x + a.z0;
 	const uint32_t nn = min(a.n_nodes[zi], a.ncap[zi]);
 	if (threadIdx.x == 0) s_nstart = 0;
 	__syncthreads();
-	if (nn * 4u <= lds_bytes) trail_components_slice<true>(a, zi, s_trail, nn, s_scan, &s_nstart);
-	else trail_components_slice<false>(a, zi, a.parent + a.nbase[zi], nn, s_scan, &s_nstart);
+	if (static_cast<uint64_t>(nn) * 12u <= lds_bytes) trail_components_slice<true, true>(a, zi, reinterpret_cast<uint32_t*>(s_comp + nn), s_comp, nn, s_scan, &s_nstart);
+	else if (static_cast<uint64_t>(nn) * 4u <= lds_bytes) trail_components_slice<true, false>(a, zi, reinterpret_cast<uint32_t*>(s_comp), a.compmin + a.nbase[zi], nn, s_scan, &s_nstart);
+	else trail_components_slice<false, false>(a, zi, a.parent + a.nbase[zi], a.compmin + a.nbase[zi], nn, s_scan, &s_nstart);
 }
 
 // ---- node tables of the walk ------------------------------------------------------

@@ -1,0 +1,204 @@
+"""Random access into a stream: cutout() decodes an x, y, z box on the device, CrackleArray wraps a
+stream behind numpy-style indexing (the reference's CrackleArray.__getitem__, crackle/array.py:257-285,
+which decodes the whole slices of the z-range and lets numpy crop them).  Here the device writes the
+box alone (ckl_cutout: the decode pipeline up to the run tables, then k_paint_window) and only the box
+crosses the link."""
+import operator
+from typing import Optional
+
+import numpy as np
+
+from . import _lib, codec, operations
+from .headers import CrackleHeader
+
+_SIGNED = {1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}
+
+
+def normalize_index(slices, shape):
+  """The index expression `slices` on a volume of `shape` = (sx, sy, sz) as three (start, stop, step,
+  is_int) tuples with 0 <= start <= stop <= dim and step >= 1; stop is tightened to one past the
+  last element taken.  numpy's meaning throughout (``...`` fills the axes that are not named), with
+  the stricter checks of the reference's reify_slices (crackle/array.py:450-532):
+
+    a slice start or stop outside [0, dim] after dim is added to a negative one   ValueError
+    a negative (or zero) step                                                      ValueError
+    more than one Ellipsis                                                         ValueError
+    an int outside [-dim, dim), more than three indices                            IndexError
+  """
+  if not isinstance(slices, tuple):
+    slices = (slices,)
+  n_ellipsis = sum(1 for s in slices if s is Ellipsis)
+  if n_ellipsis > 1:
+    raise ValueError("More than one Ellipsis operator used at once.")
+  named = len(slices) - n_ellipsis
+  if named > 3:
+    raise IndexError(f"too many indices for a volume: 3 axes, {named} were indexed")
+  full = []
+  for s in slices:
+    if s is Ellipsis:
+      full.extend([slice(None)] * (3 - named))
+    else:
+      full.append(s)
+  full.extend([slice(None)] * (3 - len(full)))
+
+  out = []
+  for axis, (s, dim) in enumerate(zip(full, shape)):
+    if isinstance(s, slice):
+      step = 1 if s.step is None else operator.index(s.step)
+      if step <= 0:
+        raise ValueError(f"Negative or zero step sizes are not supported. Got: {step}")
+      start = 0 if s.start is None else operator.index(s.start)
+      stop = dim if s.stop is None else operator.index(s.stop)
+      ends = []
+      for v in (start, stop):
+        if v < 0:
+          v += dim
+        if v < 0 or v > dim:
+          raise ValueError(f"Value {v} on axis {axis} cannot be outside of inclusive range 0 to {dim}")
+        ends.append(v)
+      start, stop = ends
+      count = max(0, -(-(stop - start) // step))
+      stop = start + (count - 1) * step + 1 if count else start
+      out.append((start, stop, step, False))
+    elif isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)):
+      i = int(s)
+      if i < -dim or i >= dim:
+        raise IndexError(f"index {i} is out of bounds for axis {axis} with size {dim}")
+      if i < 0:
+        i += dim
+      out.append((i, i + 1, 1, True))
+    else:
+      raise TypeError(f"cutout indices are ints, slices and Ellipsis, not {type(s).__name__}")
+  return out
+
+
+def cutout(binary: bytes, slices, label: Optional[int] = None, device: int = 0) -> np.ndarray:
+  """``decompress(binary, label=label)[slices]`` by numpy's rules, decoding only the box that
+  `slices` spans: an int, a slice, ``...`` or a tuple of up to three of them with at most one ``...``.
+  Stricter than numpy where the reference is (normalize_index): bounds are checked, not clamped, and
+  steps are positive.
+
+  One deliberate difference from the reference: its __getitem__ hands the caller's tuple, Ellipsis
+  included, to numpy after it has already cut z (crackle/array.py:270-280), so ``arr[..., 0]``
+  indexes y there.  Here ``...`` means what it means in numpy: ``arr[..., 0]`` is the first z slice.
+
+  The device decodes the slices of the box's z-range (so a damaged slice in that range raises as it
+  does for decompress, wherever the box lies) and writes the box alone; steps and int axes are
+  applied with numpy on that small result.  Streams without voxels, with a single label or asked for
+  a label they do not hold are answered on the host, as decompress_range answers them."""
+  binary = bytes(binary)
+  head = CrackleHeader.frombytes(binary)
+  idx = normalize_index(slices, (head.sx, head.sy, head.sz))
+  (x0, x1, _, _), (y0, y1, _, _), (z0, z1, _, _) = idx
+  shape = (x1 - x0, y1 - y0, z1 - z0)
+  order = "F" if head.fortran_order else "C"
+  dtype = np.dtype(_SIGNED[head.data_width] if head.signed else head.dtype)
+  if label is not None:
+    dtype = np.dtype(bool)
+
+  if shape[0] * shape[1] * shape[2] == 0:
+    box = np.zeros(shape, dtype=dtype, order=order)
+  elif label is not None and not codec.contains(binary, label):
+    box = np.zeros(shape, dtype=dtype, order=order)
+  elif label is None and codec.num_labels(binary) == 1:
+    single = codec.labels(binary)[0]
+    box = np.full(shape, single, dtype=head.dtype, order=order).view(dtype)
+  else:
+    raw = np.empty((shape[0] * shape[1] * shape[2],), dtype=np.uint8 if label is not None else head.dtype)
+    rc = _lib.lib().ckl_cutout(
+      binary, len(binary), raw.ctypes.data, raw.nbytes, _lib.MEM_HOST,
+      x0, x1, y0, y1, z0, z1, int(label is not None), int(label or 0), int(device),
+    )
+    if rc != _lib.CKL_OK:
+      codec._raise(rc)
+    box = raw.view(dtype).reshape(shape, order=order)
+  return box[tuple(0 if is_int else slice(None, None, step) for _, _, step, is_int in idx)]
+
+
+class CrackleArray:
+  """A stream behind a read-only array interface (crackle/array.py:32-285): metadata from the header
+  and the label section, ``arr[x0:x1, y0:y1, z0:z1]`` through cutout(), and the package's operations
+  as methods."""
+
+  def __init__(self, binary: bytes, device: int = 0):
+    self.binary = bytes(binary)
+    self.device = device
+    head = self.header()
+    self.shape = (head.sx, head.sy, head.sz)
+
+  def __len__(self):
+    return len(self.binary)
+
+  def header(self) -> CrackleHeader:
+    return codec.header(self.binary)
+
+  @property
+  def dtype(self):
+    head = self.header()
+    return np.dtype(_SIGNED[head.data_width] if head.signed else head.dtype)
+
+  @property
+  def size(self) -> int:
+    return self.shape[0] * self.shape[1] * self.shape[2]
+
+  @property
+  def ndim(self) -> int:
+    return len(self.shape)
+
+  @property
+  def nbytes(self) -> int:
+    return self.header().nbytes
+
+  def labels(self) -> np.ndarray:
+    return codec.labels(self.binary)
+
+  def num_labels(self) -> int:
+    return codec.num_labels(self.binary)
+
+  def __contains__(self, label: int) -> bool:
+    return codec.contains(self.binary, label)
+
+  def min(self) -> int:
+    return int(self.labels().view(self.dtype).min())
+
+  def max(self) -> int:
+    return int(self.labels().view(self.dtype).max())
+
+  def decompress(self, label: Optional[int] = None, crop: bool = False) -> np.ndarray:
+    return codec.decompress(self.binary, label=label, crop=crop, device=self.device)
+
+  def numpy(self, *args, **kwargs) -> np.ndarray:
+    return self.decompress(*args, **kwargs)
+
+  def __getitem__(self, slices) -> np.ndarray:
+    return cutout(self.binary, slices, device=self.device)
+
+  def voxel_counts(self, label: Optional[int] = None):
+    return codec.voxel_counts(self.binary, label=label, device=self.device)
+
+  def centroids(self, label: Optional[int] = None):
+    return codec.centroids(self.binary, label=label, device=self.device)
+
+  def bounding_boxes(self, label: Optional[int] = None, no_slice_conversion: bool = False):
+    return codec.bounding_boxes(self.binary, label=label, no_slice_conversion=no_slice_conversion, device=self.device)
+
+  def point_cloud(self, label=None, skip_background: bool = True, z_start: int = -1, z_end: int = -1):
+    return operations.point_cloud(self.binary, label, z_start=z_start, z_end=z_end, skip_background=skip_background, device=self.device)
+
+  def contacts(self, anisotropy=(1.0, 1.0, 1.0)):
+    return operations.contacts(self.binary, anisotropy=anisotropy, device=self.device)
+
+  def connected_components(self, connectivity: int = 26, binary_image: bool = False, return_mapping: bool = False):
+    out = operations.connected_components(self.binary, connectivity=connectivity, binary_image=binary_image, return_mapping=return_mapping, device=self.device)
+    if return_mapping:
+      return CrackleArray(out[0], self.device), out[1]
+    return CrackleArray(out, self.device)
+
+  def voxel_connectivity_graph(self, connectivity: int = 4) -> np.ndarray:
+    return codec.voxel_connectivity_graph(self.binary, connectivity, device=self.device)
+
+  def mode_pooling_2x2x1(self) -> "CrackleArray":
+    return CrackleArray(operations.mode_pooling_2x2x1(self.binary, device=self.device), self.device)
+
+  def array_equal(self, other: "CrackleArray") -> bool:
+    return operations.array_equal(self.binary, other.binary, device=self.device)

@@ -205,6 +205,9 @@ dev::RunGeom run_geom(const ckl_decoder& d);
 dev::RunArrays run_arrays(const ckl_decoder& d);
 // Goal::STATS: k_run_stats on the session's stream (ckl_operations.hip)
 void launch_run_stats(ckl_decoder& d, const dev::RunArrays& ra, const StatsArgs& sa);
+// the box [x0, x1) x [y0, y1) of the session's slices, dense, into a device buffer: a TABLES run, then
+// k_paint_window (ckl_operations.hip); bounds outside the slice and a buffer too small are CKL_ERR_ARG
+void decoder_cutout(ckl_decoder& d, int64_t x0, int64_t x1, int64_t y0, int64_t y1, void* out_device, uint64_t capacity, int has_label, uint64_t label);
 
 // f(LabelType<T>()) with T the unsigned type of `width` bytes (1, 2, 4, else 8)
 template <typename T> struct LabelType { typedef T type; };

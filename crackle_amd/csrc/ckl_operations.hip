@@ -404,6 +404,144 @@ __global__ void __launch_bounds__(kBlock) k_mode_pool_2x2(const LABEL* __restric
 	out[i] = v;
 }
 
+// ------------------------------------------------------------------------------
+// cutout (crackle/array.py:257-285): the labels of an x, y box of every slice of the range.  The
+// reference decodes the whole slices and lets numpy crop them; here a paint over the run tables
+// writes the box alone, dense, laid out as a decode of a volume that was the box.
+// One workgroup per (tile of whole window rows, slice).  The runs a window row crosses are
+// consecutive run indices (runs are numbered in raster order): wave 0 finds every row's first and
+// last run from word_base and the vertical-crack plane, the labels of those runs (run -> component
+// -> label: two dependent loads per run, not per pixel) are staged in LDS row after row, then every
+// thread takes chunks of 16 output bytes of consecutive window pixels.  A chunk is aligned to 16
+// bytes in the OUTPUT (rows of the box start at any element), so whole chunks are one vector store
+// and only the head and the tail of a row go pixel by pixel.  A tile whose rows cross more than
+// kWinStage runs (noise) looks every pixel's label up in HBM instead.  Streams that are not
+// fortran_order get z fastest, pixel by pixel: correct, not fast.
+// Everything read from the tables is clamped: a run to the slice's last one, a component past the
+// count of the label section to label 0, as k_paint_runs and k_run_labels do.
+// ------------------------------------------------------------------------------
+constexpr uint32_t kWinTile = 4096;       // window pixels per workgroup, in whole rows
+constexpr uint32_t kWinRows = kWave;      // most rows of a tile: wave 0 holds one row per lane
+constexpr uint32_t kWinStage = 1536;      // run labels staged per workgroup
+
+struct WindowArgs {
+	uint32_t x0, x1, y0, y1;      // the box in pixels of the slice, x0 < x1 <= sx, y0 < y1 <= sy
+	uint32_t rows;                // window rows per tile, 1 .. kWinRows
+	uint32_t nslices;
+	uint32_t fortran_order;
+	uint32_t has_label;           // one byte per voxel: 1 where the label is `label`
+	uint64_t label;
+};
+
+// grid = (ceil((y1 - y0) / rows), nslices), block = kBlock
+template <typename OUT>
+__global__ void __launch_bounds__(kBlock) k_paint_window(
+	RunGeom g, RunArrays ra, const uint64_t* __restrict__ label_map, const uint64_t* __restrict__ comp_off,
+	const uint32_t* __restrict__ ncomp_expect, WindowArgs wa, OUT* __restrict__ out
+) {
+	constexpr uint32_t V = 16 / sizeof(OUT);      // pixels of a chunk
+	struct alignas(16) Chunk { OUT v[V]; };
+	__shared__ OUT s_lab[kWinStage];
+	__shared__ uint32_t s_lo[kWinRows], s_off[kWinRows + 1];      // per row: its first run, where its labels start in s_lab
+	const uint32_t t = threadIdx.x;
+	const uint32_t zi = blockIdx.y;
+	const uint32_t wx = wa.x1 - wa.x0, wy = wa.y1 - wa.y0;
+	const uint32_t r0 = blockIdx.x * wa.rows;
+	const uint32_t rows = min(wa.rows, wy - r0);
+	const uint32_t nruns = ra.nruns[zi];
+	const uint32_t last = nruns ? nruns - 1u : 0u;
+	const uint32_t nce = ncomp_expect[zi];
+	const uint32_t* rcc = ra.run_cc + ra.rbase[zi];
+	const uint64_t* lmap = label_map + comp_off[zi];
+	const uint32_t* wb = ra.word_base + zi * g.plane_words;
+	auto label_of = [&](uint32_t run) -> OUT {      // run <= last
+		if (!nruns) return static_cast<OUT>(0);
+		const uint32_t cc = rcc[run];
+		uint64_t v = cc < nce ? lmap[cc] : 0ull;
+		if (wa.has_label) v = (v == wa.label);
+		return static_cast<OUT>(v);
+	};
+	if (t < kWave) {
+		uint32_t lo = 0, n = 0;
+		if (t < rows) {
+			const uint32_t y = wa.y0 + r0 + t, xe = wa.x1 - 1u;
+			lo = min(wb[y * g.row_words + (wa.x0 >> 5)] + __popc(g.breaks(zi, y, wa.x0 >> 5) & mask_le(wa.x0 & 31u)) - 1u, last);
+			const uint32_t hi = min(wb[y * g.row_words + (xe >> 5)] + __popc(g.breaks(zi, y, xe >> 5) & mask_le(xe & 31u)) - 1u, last);
+			n = hi >= lo ? hi - lo + 1u : 1u;
+		}
+		uint32_t end = n;      // inclusive scan over the rows
+		for (uint32_t d = 1; d < kWave; d <<= 1) {
+			const uint32_t o = __shfl_up(end, d, kWave);
+			if (t >= d) end += o;
+		}
+		if (t < rows) { s_lo[t] = lo; s_off[t + 1] = end; }
+		if (t == 0) s_off[0] = 0;
+	}
+	__syncthreads();
+	const uint32_t total = s_off[rows];
+	const bool staged = total <= kWinStage;
+	if (staged) {
+		for (uint32_t i = t; i < total; i += kBlock) {
+			uint32_t r = 0, hi = rows;      // the row of entry i: the last one that starts at or before it
+			while (r + 1 < hi) {
+				const uint32_t mid = (r + hi) >> 1;
+				if (s_off[mid] <= i) r = mid; else hi = mid;
+			}
+			s_lab[i] = label_of(min(s_lo[r] + (i - s_off[r]), last));
+		}
+	}
+	__syncthreads();
+	// V pixels per 16 bytes of output; a row has a partial chunk in front when it does not start on 16 bytes
+	const uint32_t cpr = (wx + V - 1u) / V + 1u;
+	const uint32_t nchunks = rows * cpr;
+	const uintptr_t base = reinterpret_cast<uintptr_t>(out);
+	const bool vec_ok = wa.fortran_order && base % sizeof(OUT) == 0;
+	for (uint32_t ci = t; ci < nchunks; ci += kBlock) {
+		const uint32_t r = ci / cpr, c = ci - r * cpr;
+		const uint32_t wr = r0 + r;
+		const uint64_t e0 = (static_cast<uint64_t>(zi) * wy + wr) * wx;      // fortran_order: the row's first element
+		const uint32_t mis = vec_ok ? static_cast<uint32_t>((base / sizeof(OUT) + e0) % V) : 0u;
+		const uint32_t a = c ? c * V - mis : 0u;
+		const uint32_t b = min(wx, (c + 1u) * V - mis);
+		if (a >= b) continue;
+		const uint32_t n = b - a;
+		const uint32_t y = wa.y0 + wr, x = wa.x0 + a, w = x >> 5, sh = x & 31u;
+		const uint32_t bw = g.breaks(zi, y, w);
+		uint64_t bits = bw >> sh;      // bit j: a run starts at pixel x + j
+		if (sh + n > 32u) bits |= static_cast<uint64_t>(g.breaks(zi, y, w + 1u)) << (32u - sh);      // pixel x + n - 1 lies in word w + 1
+		uint32_t run = min(wb[y * g.row_words + w] + __popc(bw & mask_le(sh)) - 1u, last);
+		Chunk ch;
+		if (staged) {
+			const uint32_t lo = s_lo[r], k0 = s_off[r], kmax = s_off[r + 1] - 1u;
+			uint32_t k = min(k0 + (run >= lo ? run - lo : 0u), kmax);
+#pragma unroll
+			for (uint32_t j = 0; j < V; j++) {
+				if (j) k = min(k + static_cast<uint32_t>((bits >> j) & 1u), kmax);
+				ch.v[j] = s_lab[k];
+			}
+		}
+		else {
+#pragma unroll
+			for (uint32_t j = 0; j < V; j++) {
+				if (j) run = min(run + static_cast<uint32_t>((bits >> j) & 1u), last);
+				ch.v[j] = j < n ? label_of(run) : static_cast<OUT>(0);
+			}
+		}
+		if (wa.fortran_order) {
+			OUT* dst = out + e0 + a;
+			if (n == V && vec_ok) *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&ch);
+			else {
+#pragma unroll
+				for (uint32_t j = 0; j < V; j++) if (j < n) dst[j] = ch.v[j];
+			}
+		}
+		else {
+#pragma unroll
+			for (uint32_t j = 0; j < V; j++) if (j < n) out[(static_cast<uint64_t>(a + j) * wy + wr) * wa.nslices + zi] = ch.v[j];
+		}
+	}
+}
+
 }  // namespace ckl
 
 using namespace ckl;
@@ -959,9 +1097,100 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 	if (prof) fprintf(stderr, "[ckl point_cloud ms]%s | contours=%zu points=%llu walk_steps=%llu\n", marks.c_str(), kept.size(), static_cast<unsigned long long>(total_points), static_cast<unsigned long long>(walk_steps));
 }
 
+// 0 <= a <= b <= dim, or CKL_ERR_ARG naming the axis: nothing is clamped (check_bounds, crackle/array.py:529-532)
+void check_box_axis(const char* axis, int64_t a, int64_t b, uint32_t dim) {
+	if (a < 0 || a > b || b > static_cast<int64_t>(dim))
+		throw Error(CKL_ERR_ARG, std::string("crackle_amd: cutout: ") + axis + " range " + std::to_string(a) + " - " + std::to_string(b) + " is not an ascending range inside 0 - " + std::to_string(dim));
+}
+
 }  // namespace
 
+namespace ckl {
+
+// The box [x0, x1) x [y0, y1) of every slice of the session's range into a device buffer, dense
+// (fortran_order streams: x fastest; others: z fastest), data_width bytes per voxel or one byte with
+// has_label.  One pipeline run up to the run tables and the component -> label map, so a damaged slice
+// of the range raises as for a decode wherever the box lies, then k_paint_window.
+void decoder_cutout(ckl_decoder& d, int64_t x0, int64_t x1, int64_t y0, int64_t y1, void* out_device, uint64_t capacity, int has_label, uint64_t label) {
+	const Header& h = d.head;
+	check_box_axis("x", x0, x1, h.sx);
+	check_box_axis("y", y0, y1, h.sy);
+	const int ow = has_label ? 1 : h.data_width;
+	const uint64_t wx = static_cast<uint64_t>(x1 - x0), wy = static_cast<uint64_t>(y1 - y0);
+	const uint64_t need = wx * wy * d.nslices * static_cast<uint64_t>(ow);
+	if (need == 0 || d.sxy == 0) return;
+	if (!out_device || capacity < need) throw Error(CKL_ERR_ARG, "crackle_amd: output buffer too small: need " + std::to_string(need) + " bytes");
+	decoder_run(d, { Goal::TABLES });
+	hipStream_t s = d.stream;
+	WindowArgs wa;
+	wa.x0 = static_cast<uint32_t>(x0); wa.x1 = static_cast<uint32_t>(x1); wa.y0 = static_cast<uint32_t>(y0); wa.y1 = static_cast<uint32_t>(y1);
+	wa.rows = static_cast<uint32_t>(std::min<uint64_t>(std::min<uint64_t>(kWinRows, wy), std::max<uint64_t>(1, kWinTile / wx)));
+	wa.nslices = d.nslices;
+	wa.fortran_order = h.fortran_order ? 1u : 0u;
+	wa.has_label = has_label ? 1u : 0u; wa.label = label;
+	const dim3 grid(static_cast<uint32_t>((wy + wa.rows - 1) / wa.rows), d.nslices);
+	// the paint as one more stage of the run's table (ckl_decoder_stage_timing), between two events of its own:
+	// the pipeline's last event lies before the host has read the slices' verdicts
+	const int st = d.n_stages;
+	const bool timed = d.stage_events && st + 2 <= kMaxStages;
+	if (timed) CKL_HIP(hipEventRecord(d.ev[st + 1], s));
+	with_label_type(ow, [&](auto t) {
+		typedef typename decltype(t)::type OUT;
+		hipLaunchKernelGGL(k_paint_window<OUT>, grid, dim3(kBlock), 0, s, run_geom(d), run_arrays(d), d.d_label_map.p, d.d_comp_off.p, d.d_ncomp_expect.p, wa, reinterpret_cast<OUT*>(out_device));
+	});
+	if (timed) CKL_HIP(hipEventRecord(d.ev[st + 2], s));
+	record_span(d);
+	CKL_HIP(hipGetLastError());
+	if (timed) {
+		CKL_HIP(hipEventElapsedTime(&d.stage_ms[st], d.ev[st + 1], d.ev[st + 2]));
+		d.stage_name[st] = "k_paint_window";
+		d.n_stages = st + 1;
+	}
+}
+
+}  // namespace ckl
+
 extern "C" {
+
+int ckl_decoder_cutout(ckl_decoder* d, int64_t x0, int64_t x1, int64_t y0, int64_t y1, void* out_device, uint64_t out_capacity_bytes, int has_label, uint64_t label) {
+	return guard([&] {
+		enter(d);
+		decoder_cutout(*d, x0, x1, y0, y1, out_device, out_capacity_bytes, has_label, label);
+	});
+}
+
+int ckl_cutout(
+	const uint8_t* buf, uint64_t n, void* out, uint64_t out_capacity_bytes, int out_mem,
+	int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1,
+	int has_label, uint64_t label, int device
+) {
+	return guard([&]() -> int {
+		if (!buf) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		const Header h = Header::parse(buf, n);
+		check_box_axis("x", x0, x1, h.sx);
+		check_box_axis("y", y0, y1, h.sy);
+		check_box_axis("z", z0, z1, h.sz);
+		const uint64_t need = static_cast<uint64_t>(x1 - x0) * static_cast<uint64_t>(y1 - y0) * static_cast<uint64_t>(z1 - z0) * static_cast<uint64_t>(has_label ? 1 : h.data_width);
+		if (need == 0) return CKL_OK;
+		if (!out || out_capacity_bytes < need) throw Error(CKL_ERR_ARG, "crackle_amd: output buffer too small: need " + std::to_string(need) + " bytes");
+		// whole planes: the decode itself, which keeps the strip kernels
+		if (x0 == 0 && x1 == h.sx && y0 == 0 && y1 == h.sy) return ckl_decompress(buf, n, out, out_capacity_bytes, out_mem, z0, z1, has_label, label, device);
+		DecoderPtr d;
+		const int rc = open_decoder(buf, n, z0, z1, device, d);
+		if (rc != CKL_OK) return rc;
+		if (out_mem == CKL_MEM_DEVICE) {
+			enter(d.get());
+			decoder_cutout(*d, x0, x1, y0, y1, out, out_capacity_bytes, has_label, label);
+		}
+		else {
+			DevBuf<uint8_t> tmp;      // the box alone, on the card and over the link
+			tmp.ensure(need);
+			decoder_cutout(*d, x0, x1, y0, y1, tmp.p, need, has_label, label);
+			CKL_HIP(hipMemcpy(out, tmp.p, need, hipMemcpyDeviceToHost));
+		}
+		return CKL_OK;
+	});
+}
 
 int ckl_decoder_label_stats(ckl_decoder* d, uint64_t capacity, uint64_t* labels, uint64_t* counts, uint64_t* sums, uint32_t* boxes, uint64_t* n_labels) {
 	return guard([&] {

@@ -206,6 +206,28 @@ int ckl_decoder_label_stats(
  * reference adds one float32 area per face instead; areas are the caller's (nx * wy * wz +
  * ny * wx * wz + nz * wx * wy). */
 int ckl_decoder_contacts(ckl_decoder* d, uint64_t** pairs, uint64_t** faces, uint64_t* n_pairs);
+/* Random access to an x, y, z box: replaces CrackleArray.__getitem__ (crackle/array.py:257-285), which
+ * decodes the whole slices of the z-range and lets numpy crop them.  The pipeline runs up to the run
+ * tables and the component -> label map over the session's z-range (so a damaged slice of the range is
+ * reported exactly as by a decode, wherever the box lies), then one kernel paints the pixels
+ * [x0, x1) x [y0, y1) of every slice and nothing else.  The output is dense, laid out as ckl_decompress
+ * lays out a volume that was the box: wx = x1 - x0, wy = y1 - y0, wz slices; fortran_order streams
+ * out[((z - z0) * wy + (y - y0)) * wx + (x - x0)], others out[((x - x0) * wy + (y - y0)) * wz + (z - z0)];
+ * data_width bytes per voxel, or one byte (1 where the label is `label`) with has_label.
+ * Bounds: 0 <= x0 <= x1 <= sx and likewise y (and z for ckl_cutout), else CKL_ERR_ARG with the axis in
+ * ckl_last_error; nothing is clamped (check_bounds, crackle/array.py:529-532).  A capacity below
+ * wx * wy * wz * width is CKL_ERR_ARG; an empty box writes nothing and is CKL_OK.
+ * ckl_decoder_cutout writes into a DEVICE buffer and reports the kernel as the last stage of
+ * ckl_decoder_stage_timing.  (No counterpart in the reference's C++: its binding has no such entry.) */
+int ckl_decoder_cutout(ckl_decoder* d, int64_t x0, int64_t x1, int64_t y0, int64_t y1,
+                       void* out_device, uint64_t out_capacity_bytes, int has_label, uint64_t label);
+/* The one-shot form of ckl_decoder_cutout (crackle/array.py:257-285) over slices [z0, z1): for
+ * CKL_MEM_HOST the box alone is allocated on the device and copied to `out`, not the slices it was cut
+ * from.  A box that spans the whole plane (x0 = 0, x1 = sx, y0 = 0, y1 = sy) is ckl_decompress of the
+ * z-range. */
+int ckl_cutout(const uint8_t* buf, uint64_t n, void* out, uint64_t out_capacity_bytes, int out_mem,
+               int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1,
+               int has_label, uint64_t label, int device);
 /* Elapsed device time of the last run, from HIP events recorded on the library's
  * own stream around (a) the whole pipeline and (b) the dominant kernel. */
 int ckl_decoder_last_timing(const ckl_decoder* d, float* pipeline_ms, float* dominant_kernel_ms);

@@ -164,6 +164,22 @@ struct DevBuf {
 	size_t bytes() const { return n * sizeof(T); }
 };
 
+template <typename T>
+inline void upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
+	d.ensure(h.size());
+	if (!h.empty()) CKL_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+}
+
+// f(LabelType<T>()) with T the unsigned type of `width` bytes (1, 2, 4, else 8)
+template <typename T> struct LabelType { typedef T type; };
+template <typename F>
+inline void with_label_type(int width, F&& f) {
+	if (width == 1) f(LabelType<uint8_t>());
+	else if (width == 2) f(LabelType<uint16_t>());
+	else if (width == 4) f(LabelType<uint32_t>());
+	else f(LabelType<uint64_t>());
+}
+
 void set_last_error(const std::string& msg);
 int select_device(int device);   // throws CKL_ERR_NO_DEVICE
 

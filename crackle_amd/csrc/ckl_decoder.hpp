@@ -141,12 +141,6 @@ struct ckl_decoder {
 
 namespace ckl {
 
-template <typename T>
-inline void upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
-	d.ensure(h.size());
-	if (!h.empty()) CKL_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
 // a stored label value, sign-extended as label_map holds it
 inline uint64_t read_stored(const Header& h, const uint8_t* lb, uint64_t offset) {
 	const int w = h.stored_data_width;
@@ -208,15 +202,5 @@ void launch_run_stats(ckl_decoder& d, const dev::RunArrays& ra, const StatsArgs&
 // the box [x0, x1) x [y0, y1) of the session's slices, dense, into a device buffer: a TABLES run, then
 // k_paint_window (ckl_operations.hip); bounds outside the slice and a buffer too small are CKL_ERR_ARG
 void decoder_cutout(ckl_decoder& d, int64_t x0, int64_t x1, int64_t y0, int64_t y1, void* out_device, uint64_t capacity, int has_label, uint64_t label);
-
-// f(LabelType<T>()) with T the unsigned type of `width` bytes (1, 2, 4, else 8)
-template <typename T> struct LabelType { typedef T type; };
-template <typename F>
-inline void with_label_type(int width, F&& f) {
-	if (width == 1) f(LabelType<uint8_t>());
-	else if (width == 2) f(LabelType<uint16_t>());
-	else if (width == 4) f(LabelType<uint32_t>());
-	else f(LabelType<uint64_t>());
-}
 
 }  // namespace ckl

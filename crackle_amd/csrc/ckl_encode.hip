@@ -10,10 +10,9 @@
 //   cc3d::connected_components2d_4 + relabel        src/cc3d.hpp:114-144, 257-369        ckl_runs.hpp (runs of the label planes)
 //   labels::encode_flat                             src/labels.hpp:30-155      k_run_resolve (crc), k_mapping_comps + sort/unique
 //   stream assembly                                 src/crackle.hpp:171-216    host
-#include "ckl_common.hpp"
+#include "ckl_encoder.hpp"
 #include "ckl_runs.hpp"
 #include "ckl_trail.hpp"
-#include "ckl_pins_dev.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -720,7 +719,6 @@ __global__ void __launch_bounds__(kBlock) k_mapping_comps(
 	mapping[comp_off[zi] + c] = static_cast<uint64_t>(labels[zi * sxy + r.comp_pix[r.rbase[zi] + c]]);
 }
 
-
 // Global component id of every voxel (cc3d.hpp:371-400 numbers components continuously
 // across slices) for the pin encoder: one thread per pixel, its run found by a popcount in
 // the row's break word, ids read from the run tables.  grid = (ceil(sxy / 256), nslices)
@@ -1115,6 +1113,28 @@ __global__ void __launch_bounds__(kBlock) k_copy_bytes(const uint8_t* __restrict
 	}
 }
 
+// grid = slices, block = kBlock: the walk's events of a slice by kind, and the longest run of events that take no decision
+// (a node with one remaining edge is left by it, a dead end returns: kEvSeg / kEvDead / kEvEnd; only kEvBseg picks an edge
+// AND leaves one behind).  counts: [slices][5] = seg, bseg, dead, end, longest run without a kEvBseg
+__global__ void __launch_bounds__(kBlock) k_trail_step_kinds(const uint32_t* __restrict__ events, const uint64_t* __restrict__ ibase, const uint32_t* __restrict__ n_events, uint32_t* __restrict__ counts) {
+	__shared__ uint32_t s_c[5];
+	const uint32_t zi = blockIdx.x;
+	if (threadIdx.x < 5) s_c[threadIdx.x] = 0u;
+	__syncthreads();
+	const uint32_t n = n_events[zi] & ~(dev::kEvFormatAddr12 | dev::kEvWalkWide);
+	const uint32_t* ev = events + ibase[zi];
+	uint32_t c[4] = { 0, 0, 0, 0 };
+	for (uint32_t i = threadIdx.x; i < n; i += kBlock) c[ev[i] >> 30]++;
+	for (int k = 0; k < 4; k++) if (c[k]) atomicAdd(&s_c[k], c[k]);
+	if (threadIdx.x == 0) {      // (one thread: a diagnostic, not a product path)
+		uint32_t run = 0, longest = 0;
+		for (uint32_t i = 0; i < n; i++) { if ((ev[i] >> 30) == 1u) run = 0; else { run++; longest = run > longest ? run : longest; } }
+		s_c[4] = longest;
+	}
+	__syncthreads();
+	if (threadIdx.x < 5) counts[zi * 5u + threadIdx.x] = s_c[threadIdx.x];
+}
+
 }  // namespace ckl
 
 // ------------------------------------------------------------------------------
@@ -1156,127 +1176,8 @@ static void copy_bytes_device(const uint8_t* src, uint8_t* dst, uint64_t n, hipS
 	hipLaunchKernelGGL(k_copy_bytes, dim3(blocks), dim3(kBlock), 0, s, src, dst, n);
 }
 
-struct VolumeStats { uint64_t max_label = 0, pairs = 0, first = 0, last = 0; };
-
-struct ckl_encoder {
-	int device = 0;
-	hipStream_t stream = nullptr;      // crack codes
-	hipStream_t stream2 = nullptr;     // labels (components, crcs, label table), concurrent with the crack trail
-	hipEvent_t ev0 = nullptr, ev1 = nullptr, evk0 = nullptr, evk1 = nullptr, ev_in = nullptr;
-	hipEvent_t evd0 = nullptr, evd1 = nullptr;      // around k_trail_walk
-	float trail_ms = 0.f;
-	hipEvent_t ev_prezero = nullptr;   // trail_prezero()'s fills on stream2 are done
-	float pipeline_ms = 0.f, dominant_ms = 0.f;
-	int64_t max_sx = 0, max_sy = 0, max_sz = 0;
-	int dtype_bytes = 0;
-
-	DevBuf<unsigned long long> d_stats;
-	DevBuf<uint4> d_adjm;                        // crack graph in micro-tiles (ckl_trail.hpp)
-	DevBuf<uint32_t> d_slice_err;
-	DevBuf<uint64_t> d_cbase, d_sbase, d_kbase, d_pbase, d_bbase, d_out_off, d_comp_off;
-	DevBuf<uint32_t> d_ccap, d_scap, d_kcap;
-	DevBuf<uint8_t> d_crack_tables;               // packed block behind the per-slice base / capacity tables of crack_pass
-	DevBuf<uint8_t> d_cp, d_fcode, d_dcode, d_payload, d_boc, d_codes_out, d_model;
-	DevBuf<uint32_t> d_code_report;
-	uint64_t codes_capacity = 0;        // bound of all slices' BOC + payload bytes
-	bool defer_codes = false;           // ckl_encoder_defer_codes: the codes stay in d_codes_out for ckl_encoder_codes_to_host
-	bool keep_device_stream = false;    // ckl_encoder_keep_device_stream: every run also assembles the whole stream in HBM
-	bool async_host_copy = false;       // ckl_encoder_async_host_copy: a run returns when the stream is complete in HBM; its crack codes reach the host buffer on stream_copy
-	bool host_copy_pending = false;     // ... until ckl_encoder_host_wait
-	hipStream_t stream_copy = nullptr;
-	hipStream_t stream_tab = nullptr;   // the pin stage's label lists come to the host beside the passes of the label stream
-	hipEvent_t ev_codes = nullptr;
-	void* tables_staging = nullptr;              // pinned host image of d_crack_tables (crack_pass: UploadPacker::commit)
-	bool uploads_by_kernel = false;              // this run's small uploads go by upload_small's kernel (flat label streams)
-	hipEvent_t ev_labels_crc = nullptr;          // the label section's crc32c stands in d_labels_crc (device-resident streams: ckl_encoder_run)
-	DevBuf<uint32_t> d_labels_crc;               // [0]: the crc, [1 ..]: the workgroups' states
-	DevBuf<uint8_t> d_stream_out;       // ... here (valid until the next run)
-	uint64_t device_stream_bytes = 0;
-	uint64_t last_codes_total = 0;      // bytes of the last run's crack codes
-	DevBuf<uint32_t> d_stack_node, d_stack_code;
-	DevBuf<uint32_t> d_chain_node, d_chain_off, d_chain_clen, d_chain_order, d_chain_dst, d_chain_vstart;
-	DevBuf<uint32_t> d_n_chains, d_n_raw, d_n_valid, d_payload_len, d_boc_len;
-	DevBuf<uint32_t> d_hist;
-	// label planes + run-based CCL (ckl_runs.hpp)
-	DevBuf<uint32_t> d_planes, d_count_vh;
-	uint32_t row_words = 0;
-	uint64_t plane_words = 0;
-	std::vector<uint32_t> count_v, count_h;     // differing neighbour pairs per slice (host copy)
-	DevBuf<uint64_t> d_rbase;
-	DevBuf<uint32_t> d_rcap, d_word_base, d_parent, d_run_start, d_run_cc, d_comp_pix, d_nruns, d_ncomp, d_idbits, d_blk_roots;
-	DevBuf<uint16_t> d_run_local;
-	DevBuf<uint32_t> d_G, d_crc_acc;
-	DevBuf<uint32_t> d_flat_report;     // [4][nslices]: ncomp | crc_acc | idbits | slice_err2 (views above)
-	uint64_t g_table_pixels = 0;                // slice size the G table was built for
-	DevBuf<uint64_t> d_mapping, d_sorted, d_uniq, d_label_hash, d_label_list;
-	DevBuf<uint8_t> d_keys;
-	DevBuf<uint32_t> d_cc_volume;                // global component id of every voxel (pin encoding only)
-	DevBuf<uint32_t> d_pin_kept, d_pin_u32;      // pin passes (ckl_pins_dev.hpp): kept-run marks (uint16 per voxel), per-component depths
-	DevBuf<uint8_t> d_pin_tables;                // per-row label tables of k_pin_dedup
-	DevBuf<uint64_t> d_pin_u64;                  // per-component keys
-	DevBuf<uint32_t> d_slice_err2, d_n_uniq, d_uniq_blk;
-	DevBuf<uint8_t> d_labels_bin;                // the flat label section, assembled on device
-	uint32_t flat_max_rcap = 0;
-	// label planes left by ckl_encoder_stats for the ckl_encoder_run that follows on the same
-	// volume (the sharded encoder: stats -> all-gather -> run with the agreed formats)
-	const void* planes_for = nullptr;
-	// ckl_encoder_markov_stats leaves the whole trail behind (difference codes, chains, BOC index): the run that
-	// follows for the same volume and crack format only packs them under the agreed model (single use, like the planes)
-	const void* trail_for = nullptr;
-	bool trail_perm = false;
-	int trail_order = 0;
-	VolumeStats planes_stats;          // max / pairs of the volume the cached planes were built from
-	int64_t planes_dims[3] = { 0, 0, 0 };
-	std::vector<uint64_t> h_rbase;
-	std::vector<uint32_t> h_rcap;
-	// trail graph (ckl_trail.hpp)
-	std::vector<uint32_t> count_special, count_corner;
-	DevBuf<uint32_t> d_plane_partial, t_blk_special, t_blk_corner;
-	DevBuf<unsigned long long> d_plane_partial_max, d_plane_out;
-	uint32_t graph_blocks = 0;
-	uint32_t tiles_x = 0, tiles_y = 0, mtx2 = 0;
-	uint64_t adjm_stride = 0;
-	bool graph_permissible = false;
-	bool planes_deferred = false;      // planes_pass left its counts on the device: graph_pass (or planes_collect) fetches them
-	bool trail_zeroed = false;         // trail_prezero() ran on the stream since the last trail: crack_pass skips its fills
-	DevBuf<uint64_t> t_nbase, t_cobase, t_ibase;
-	DevBuf<uint32_t> t_ncap, t_cocap, t_icap, t_max_steps;
-	size_t last_trail_slices = 0;                // slices of the last crack pass (the layout of t_counters)
-	DevBuf<uint32_t> t_counters;                 // n_nodes | n_snap | n_corners | n_starts | n_items | n_events | seg_len_sum, [nslices] each
-	DevBuf<uint32_t> t_node_vertex, t_vert2node, t_corner_vertex;
-	DevBuf<uint8_t> t_node_adj;
-	DevBuf<uint32_t> t_dart_end, t_dart_len, t_dart_minv, t_dart_minpos, t_parent, t_start_bits, t_starts;
-	DevBuf<uint4> t_dart_codes;
-	DevBuf<uint8_t> t_dart_inline;
-	DevBuf<unsigned long long> t_compmin;
-	DevBuf<uint32_t> t_items, t_item_off, t_chain_item0, t_events, t_chain_ev0, t_ev_lnd, t_ev_item;
-
-	~ckl_encoder() {
-		if (ev0) (void)hipEventDestroy(ev0);
-		if (ev1) (void)hipEventDestroy(ev1);
-		if (evk0) (void)hipEventDestroy(evk0);
-		if (evk1) (void)hipEventDestroy(evk1);
-		if (evd0) (void)hipEventDestroy(evd0);
-		if (evd1) (void)hipEventDestroy(evd1);
-		if (ev_in) (void)hipEventDestroy(ev_in);
-		if (ev_prezero) (void)hipEventDestroy(ev_prezero);
-		if (stream) (void)hipStreamDestroy(stream);
-		if (stream2) (void)hipStreamDestroy(stream2);
-		if (stream_copy) { (void)hipStreamSynchronize(stream_copy); (void)hipStreamDestroy(stream_copy); }
-		if (stream_tab) { (void)hipStreamSynchronize(stream_tab); (void)hipStreamDestroy(stream_tab); }
-		if (ev_codes) (void)hipEventDestroy(ev_codes);
-		if (tables_staging) host_out_free(tables_staging);
-		if (ev_labels_crc) (void)hipEventDestroy(ev_labels_crc);
-	}
-};
-
 namespace {
 
-template <typename T>
-void upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
-	d.ensure(h.size());
-	if (!h.empty()) CKL_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-}
 // Many small tables in ONE copy: the tables become views of a packed block (a copy of a few bytes costs
 // ~8 us of stream time, and crack_pass needs fifteen of them between two kernels of the trail).
 struct UploadPacker {
@@ -1307,15 +1208,6 @@ struct UploadPacker {
 	}
 };
 
-template <typename T>
-std::vector<T> download(const T* p, size_t n, hipStream_t s) {
-	std::vector<T> h(n);
-	if (n) CKL_HIP(hipMemcpyAsync(h.data(), p, n * sizeof(T), hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipStreamSynchronize(s));
-	return h;
-}
-
-
 template <typename LABEL>
 VolumeStats volume_stats(ckl_encoder& e, const LABEL* labels, uint64_t voxels) {
 	VolumeStats st;
@@ -1334,38 +1226,22 @@ VolumeStats volume_stats(ckl_encoder& e, const LABEL* labels, uint64_t voxels) {
 	return st;
 }
 
-// wall-clock breakdown of the host side, printed when CKL_PROFILE is set
-struct HostTimer {
-	bool on;
-	std::chrono::steady_clock::time_point t0;
-	std::vector<std::pair<const char*, double>> marks;
-	HostTimer() : on(getenv("CKL_PROFILE") != nullptr), t0(std::chrono::steady_clock::now()) {}
-	void mark(const char* name) {
-		if (!on) return;
-		auto t1 = std::chrono::steady_clock::now();
-		marks.emplace_back(name, std::chrono::duration<double, std::milli>(t1 - t0).count());
-		t0 = t1;
-	}
-	~HostTimer();
-};
-thread_local HostTimer* g_ht = nullptr;
-#define HT_MARK(name) do { if (g_ht) g_ht->mark(name); } while (0)
-inline HostTimer::~HostTimer() {
-		g_ht = nullptr;
-		if (!on) return;
-		fprintf(stderr, "[ckl encode host ms]");
-		for (auto& m : marks) fprintf(stderr, " %s=%.2f", m.first, m.second);
-		fprintf(stderr, "\n");
+// the label planes of the session, V then H, as the kernels take them
+inline uint32_t* plane_v(const ckl_encoder& e) { return e.d_planes.p; }
+inline uint32_t* plane_h(const ckl_encoder& e, uint32_t ns) { return e.d_planes.p + e.plane_words * ns; }
+
+// ckl_encoder_stats left the planes of exactly this volume behind (single use: the callers clear planes_for)
+inline bool planes_cached(const ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, int64_t sz) {
+	return e.planes_for == labels && e.planes_dims[0] == sx && e.planes_dims[1] == sy && e.planes_dims[2] == sz;
 }
 
-// One pass over the labels -> the two "differs from neighbour" bit planes and their
-// per-slice population counts (exact crack edge and run counts follow from these).
-template <typename LABEL>
-VolumeStats volume_stats(ckl_encoder& e, const LABEL* labels, uint64_t voxels);
+// crack edges of slice zi, exactly: the interior pixel pairs that differ (IMPERMISSIBLE) or are equal (PERMISSIBLE)
+inline uint64_t crack_edges(const ckl_encoder& e, int64_t sx, int64_t sy, size_t zi, bool permissible) {
+	const uint64_t interior = static_cast<uint64_t>(sx > 0 ? sx - 1 : 0) * sy + static_cast<uint64_t>(sx) * (sy > 0 ? sy - 1 : 0);
+	const uint64_t differ = static_cast<uint64_t>(e.count_v[zi]) + e.count_h[zi];
+	return permissible ? interior - differ : differ;
+}
 
-// One pass over the labels -> the two "differs from neighbour" bit planes and their
-// per-slice population counts (exact crack edge and run counts follow from these) and,
-// on the fast path, the whole-volume reductions of lib.hpp:224-256 from the same read.
 // the fast planes kernel's per-slice counts -> e.count_v / count_h and the volume's statistics
 void planes_collect(ckl_encoder& e, uint32_t ns, VolumeStats* st, const std::vector<unsigned long long>* fetched = nullptr) {
 	std::vector<unsigned long long> mine;
@@ -1401,6 +1277,9 @@ void trail_prezero(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
 	e.trail_zeroed = true;
 }
 
+// One pass over the labels -> the two "differs from neighbour" bit planes and their
+// per-slice population counts (exact crack edge and run counts follow from these) and,
+// on the fast path, the whole-volume reductions of lib.hpp:224-256 from the same read.
 template <typename LABEL>
 void planes_pass(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz, VolumeStats* st, bool defer = false) {
 	hipStream_t s = e.stream;
@@ -1422,7 +1301,7 @@ void planes_pass(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, in
 		trail_prezero(e, sx, sy, sz);
 		hipLaunchKernelGGL(k_label_planes_stream<LABEL>, dim3(nblk, ns), dim3(kBlock), 0, s,
 			labels, static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), strips, bands,
-			e.d_planes.p, e.d_planes.p + e.plane_words * ns, e.row_words, e.plane_words,
+			plane_v(e), plane_h(e, ns), e.row_words, e.plane_words,
 			e.d_plane_partial.p, e.d_plane_partial_max.p, e.d_plane_out.p + 4ull * ns);
 		hipLaunchKernelGGL(k_planes_reduce, dim3(ns), dim3(kBlock), 0, s, e.d_plane_partial.p, e.d_plane_partial_max.p, nblk, e.d_plane_out.p, e.d_plane_out.p + 4ull * ns);
 		// deferred: graph_pass fetches the counts together with its own (k_trail_graph decides the crack
@@ -1438,18 +1317,25 @@ void planes_pass(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, in
 	const uint64_t units = static_cast<uint64_t>(chunks) * sy;
 	hipLaunchKernelGGL(k_label_planes<LABEL>, dim3(static_cast<uint32_t>((units + kWaves * kPlaneUnroll - 1) / (kWaves * kPlaneUnroll)), ns), dim3(kBlock), 0, s,
 		labels, static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), chunks,
-		e.d_planes.p, e.d_planes.p + e.plane_words * ns, e.row_words, e.plane_words,
+		plane_v(e), plane_h(e, ns), e.row_words, e.plane_words,
 		e.d_count_vh.p, e.d_count_vh.p + ns);
 	std::vector<uint32_t> c = download(e.d_count_vh.p, 2 * static_cast<size_t>(ns), s);
 	e.count_v.assign(c.begin(), c.begin() + ns);
 	e.count_h.assign(c.begin() + ns, c.end());
 }
 
+// planes_pass for the session's label width
+void planes_pass_any(ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, int64_t sz, VolumeStats* st) {
+	with_label_type(e.dtype_bytes, [&](auto t) { planes_pass(e, static_cast<const typename decltype(t)::type*>(labels), sx, sy, sz, st); });
+}
+
 // crack graph (vertex nibbles in tiles, crackcodes.hpp:66-125) + the node / corner counts
 // of the trail graph (ckl_trail.hpp)
-// perm_mode: 0 impermissible, 1 permissible, 2 decided on the device from the planes kernel's pair count
-// (crackle.hpp:50-55; needs planes_deferred); `st` receives the deferred statistics
-void graph_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, int perm_mode, VolumeStats* st = nullptr) {
+// ON_DEVICE: decided on the device from the planes kernel's pair count (crackle.hpp:50-55; needs planes_deferred);
+// `st` receives the deferred statistics
+enum class GraphFormat : uint32_t { IMPERMISSIBLE = 0, PERMISSIBLE = 1, ON_DEVICE = 2 };      // (the values are k_trail_graph's)
+inline GraphFormat graph_format(bool permissible) { return permissible ? GraphFormat::PERMISSIBLE : GraphFormat::IMPERMISSIBLE; }
+void graph_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, GraphFormat format, VolumeStats* st = nullptr) {
 	hipStream_t s = e.stream;
 	const uint32_t ns = static_cast<uint32_t>(sz);
 	e.tiles_x = static_cast<uint32_t>((sx + 1 + kTrailTileDim - 1) / kTrailTileDim);
@@ -1463,12 +1349,13 @@ void graph_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, int perm_mod
 	e.t_blk_special.ensure(static_cast<size_t>(e.graph_blocks) * ns);
 	e.t_blk_corner.ensure(static_cast<size_t>(e.graph_blocks) * ns);
 	e.d_count_vh.ensure(4 * static_cast<size_t>(ns));
-	if (perm_mode == 2 && !e.planes_deferred) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: crack format left to the device without deferred counts");
+	const bool on_device = format == GraphFormat::ON_DEVICE;
+	if (on_device && !e.planes_deferred) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: crack format left to the device without deferred counts");
 	const unsigned long long half_voxels = static_cast<unsigned long long>(static_cast<int64_t>(static_cast<uint64_t>(sx) * sy * sz) / 2);
 	hipLaunchKernelGGL(k_trail_graph, dim3(e.graph_blocks, ns), dim3(kBlock), 0, s,
-		e.d_planes.p, e.d_planes.p + e.plane_words * ns, e.row_words, e.plane_words,
-		static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), static_cast<uint32_t>(perm_mode),
-		perm_mode == 2 ? e.d_plane_out.p + 4ull * ns : nullptr, half_voxels,
+		plane_v(e), plane_h(e, ns), e.row_words, e.plane_words,
+		static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), static_cast<uint32_t>(format),
+		on_device ? e.d_plane_out.p + 4ull * ns : nullptr, half_voxels,
 		reinterpret_cast<uint32_t*>(e.d_adjm.p), e.adjm_stride * 4,
 		e.mtx2, e.tiles_x, e.tiles_y, e.t_blk_special.p, e.t_blk_corner.p);
 	hipLaunchKernelGGL(k_trail_count_scan, dim3(ns), dim3(kBlock), 0, s, e.t_blk_special.p, e.t_blk_corner.p, e.graph_blocks,
@@ -1484,38 +1371,127 @@ void graph_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, int perm_mod
 	VolumeStats v;
 	if (!po.empty()) planes_collect(e, ns, &v, &po);
 	if (st && !po.empty()) *st = v;
-	e.graph_permissible = perm_mode == 2 ? static_cast<int64_t>(v.pairs) < static_cast<int64_t>(static_cast<uint64_t>(sx) * sy * sz) / 2 : perm_mode == 1;
+	e.graph_permissible = on_device ? static_cast<int64_t>(v.pairs) < static_cast<int64_t>(static_cast<uint64_t>(sx) * sy * sz) / 2 : format == GraphFormat::PERMISSIBLE;
 }
 
+// What a crack pass is asked for.  HISTOGRAM stops behind k_markov_hist (markov_order > 0): the trail stays on the
+// device.  CODES goes on through the packing, the gather and the report: the codes stay in e.d_codes_out.
+enum class CrackGoal { HISTOGRAM, CODES };
+struct CrackRequest {
+	CrackGoal goal = CrackGoal::CODES;
+	bool permissible = false;
+	int markov_order = 0;
+	const std::vector<uint8_t>* model = nullptr;      // the forced model (symbol -> rank); null: from this volume's histogram
+	bool reuse_trail = false;                          // the trail of a HISTOGRAM pass over the same planes is still there: only pack it
+	std::function<void()> overlap;                     // the label side: runs on the host while the trail kernels execute
+};
 struct CrackResult {
 	std::vector<uint32_t> code_len;     // per slice: boc + payload bytes
 	uint64_t total = 0;                 // bytes of all crack codes; they stay in e.d_codes_out
 	bool any_chain = false;
+	std::vector<uint32_t> hist;         // markov histogram (unless a model was forced)
+	std::vector<uint8_t> model;         // the model the codes were packed under
 };
 
 // Dynamic LDS of k_trail_walk for slices of up to `max_special` nodes (+ what k_trail_loops / _components add)
 inline size_t trail_walk_lds(uint32_t max_special) { return (static_cast<size_t>(max_special) + 256) * 16 + 1024; }
 
-// Runs graph + walk + finish.  When `hist_only` is set, stops after the markov
-// histogram (returned in hist).  `model` (symbol -> rank) is required for markov packing.
-void crack_pass(
-	ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, bool permissible,
-	int markov_order, bool hist_only, const std::vector<uint8_t>* model_in,
-	std::vector<uint32_t>* hist_out, std::vector<uint8_t>* model_out, CrackResult* result,
-	const std::function<void()>& overlap = std::function<void()>(), bool reuse_trail = false
-) {
+// k_finish's view of the session (the arrays are there: crack_pass has sized them)
+FinishArgs finish_args(const ckl_encoder& e, int64_t sx, int64_t sy, int markov_order) {
+	FinishArgs fa;
+	fa.sx = static_cast<int>(sx); fa.sy = static_cast<int>(sy);
+	fa.xw = byte_width(static_cast<uint64_t>(sx) + 1); fa.yw = byte_width(static_cast<uint64_t>(sy) + 1);
+	fa.markov = markov_order ? 1u : 0u;
+	fa.cbase = e.d_cbase.p; fa.kbase = e.d_kbase.p;
+	fa.n_chains = e.d_n_chains.p; fa.n_raw = e.d_n_raw.p; fa.n_valid = e.d_n_valid.p;
+	fa.cp = e.d_cp.p; fa.chain_node = e.d_chain_node.p; fa.chain_off = e.d_chain_off.p; fa.chain_clen = e.d_chain_clen.p;
+	fa.chain_order = e.d_chain_order.p; fa.chain_dst = e.d_chain_dst.p; fa.chain_vstart = e.d_chain_vstart.p;
+	fa.fcode = e.d_fcode.p; fa.dcode = e.d_dcode.p;
+	fa.pbase = e.d_pbase.p; fa.payload = e.d_payload.p; fa.bbase = e.d_bbase.p; fa.boc = e.d_boc.p;
+	fa.payload_len = e.d_payload_len.p; fa.boc_len = e.d_boc_len.p;
+	fa.z0 = 0;
+	return fa;
+}
+
+// the trail kernels' view of the session (ckl_trail.hpp), with the walk's test switches; dbg stays null
+TrailArgs trail_args(const ckl_encoder& e, int64_t sx, int64_t sy, uint32_t ns) {
+	const uint64_t nverts = static_cast<uint64_t>(sx + 1) * (sy + 1);
+	TrailArgs ta;
+	ta.adjm = e.d_adjm.p; ta.adjm_stride = e.adjm_stride; ta.mtx2 = e.mtx2; ta.tiles_x = e.tiles_x; ta.tiles_y = e.tiles_y;
+	ta.planeV = plane_v(e); ta.planeH = plane_h(e, ns); ta.row_words = e.row_words; ta.plane_words = e.plane_words;
+	ta.sx = static_cast<uint32_t>(sx); ta.sy = static_cast<uint32_t>(sy); ta.inv = e.graph_permissible ? 0xFFFFFFFFu : 0u;
+	ta.sxe = static_cast<uint32_t>(sx + 1); ta.sye = static_cast<uint32_t>(sy + 1); ta.nverts = static_cast<uint32_t>(nverts);
+	ta.max_steps = e.t_max_steps.p;
+	ta.nbase = e.t_nbase.p; ta.ncap = e.t_ncap.p;
+	ta.n_nodes = e.t_counters.p; ta.n_corners = e.t_counters.p + 2 * ns;
+	ta.n_starts = e.t_counters.p + 3 * ns; ta.n_items = e.t_counters.p + 4 * ns;
+	ta.node_vertex = e.t_node_vertex.p; ta.node_adj = e.t_node_adj.p; ta.vert2node = e.t_vert2node.p;
+	ta.cobase = e.t_cobase.p; ta.cocap = e.t_cocap.p; ta.corner_vertex = e.t_corner_vertex.p;
+	ta.dart_end = e.t_dart_end.p; ta.dart_len = e.t_dart_len.p; ta.dart_minv = e.t_dart_minv.p; ta.dart_minpos = e.t_dart_minpos.p;
+	ta.dart_codes = e.t_dart_codes.p; ta.dart_inline = e.t_dart_inline.p;
+	ta.parent = e.t_parent.p; ta.compmin = e.t_compmin.p;
+	ta.start_bits = e.t_start_bits.p; ta.start_words = static_cast<uint32_t>((nverts + 31) / 32); ta.starts = e.t_starts.p;
+	ta.ibase = e.t_ibase.p; ta.icap = e.t_icap.p; ta.items = e.t_items.p; ta.item_off = e.t_item_off.p;
+	ta.sbase = e.d_sbase.p; ta.scap = e.d_scap.p; ta.stack_node = e.d_stack_node.p; ta.stack_item = e.d_stack_code.p;
+	ta.kbase = e.d_kbase.p; ta.kcap = e.d_kcap.p;
+	ta.chain_node = e.d_chain_node.p; ta.chain_item0 = e.t_chain_item0.p; ta.chain_off = e.d_chain_off.p; ta.chain_clen = e.d_chain_clen.p;
+	ta.n_chains = e.d_n_chains.p; ta.n_raw = e.d_n_raw.p; ta.n_valid = e.d_n_valid.p;
+	ta.cbase = e.d_cbase.p; ta.ccap = e.d_ccap.p; ta.cp = e.d_cp.p; ta.slice_err = e.d_slice_err.p;
+	ta.events = e.t_events.p; ta.n_events = e.t_counters.p + 5 * ns; ta.seg_len_sum = e.t_counters.p + 6 * ns; ta.chain_ev0 = e.t_chain_ev0.p; ta.ev_lnd = e.t_ev_lnd.p; ta.ev_item = e.t_ev_item.p;
+	ta.dbg = nullptr;
+	{ const char* env = getenv("CKL_TRAIL_WALK"); ta.walk_plain = (env && !strcmp(env, "plain")) ? 1u : 0u; ta.walk_no_regs = (env && !strcmp(env, "lds")) ? 1u : 0u; }
+	{ const char* env = getenv("CKL_TRAIL_WALK_STACK"); ta.walk_stack_cap = env ? static_cast<uint32_t>(std::max(1, atoi(env))) : 0xFFFFFFFFu; }
+	ta.graph_blocks = e.graph_blocks; ta.blk_special = e.t_blk_special.p; ta.blk_corner = e.t_blk_corner.p;
+	ta.z0 = 0;
+	return ta;
+}
+
+// CKL_TRAIL_DIAG on a tuning build: what the trail's kernels counted (ta_dbg: TrailArgs::dbg, or null)
+void trail_diag(ckl_encoder& e, uint32_t ns, const unsigned long long* ta_dbg, uint32_t max_special, size_t trail_lds_used) {
+	hipStream_t s = e.stream;
+	std::vector<uint32_t> c = download(e.t_counters.p, 5 * static_cast<size_t>(ns), s);
+	double m[5] = { 0 };
+	for (int k = 0; k < 5; k++) for (uint32_t zi = 0; zi < ns; zi++) m[k] += static_cast<double>(c[static_cast<size_t>(k) * ns + zi]) / ns;
+	double sp = 0, co = 0;
+	for (uint32_t zi = 0; zi < ns; zi++) { sp += static_cast<double>(e.count_special[zi]) / ns; co += static_cast<double>(e.count_corner[zi]) / ns; }
+	if (ta_dbg) {
+		std::vector<unsigned long long> g = download(ta_dbg, 16, s);
+		if (g[11]) fprintf(stderr, "[ckl trail diag, k_trail_walk] mean cycles per slice: table fill=%.0f fill + walk=%.0f\n", static_cast<double>(g[6]) / g[11], static_cast<double>(g[7]) / g[11]);
+		if (g[11]) fprintf(stderr, "[ckl trail diag, k_trail_walk] slices=%llu iterations/slice=%.0f cycles/iteration=%.0f clock=%.2f GHz (cycles / 100 MHz ticks)\n",
+			g[11], static_cast<double>(g[8]) / g[11], g[8] ? static_cast<double>(g[9]) / g[8] : 0.0, g[10] ? static_cast<double>(g[9]) / (g[10] * 10.0) : 0.0);
+		fprintf(stderr, "[ckl trail diag, k_trail_components, mean cycles per slice] union=%.0f component minima=%.0f starts/splits=%.0f bitmap scan=%.0f\n",
+			static_cast<double>(g[12]) / ns, static_cast<double>(g[13]) / ns, static_cast<double>(g[14]) / ns, static_cast<double>(g[15]) / ns);
+		fprintf(stderr, "[ckl trail diag, k_trail_segments] waves=%llu iterations/wave mean=%.1f max=%llu cycles/wave mean=%.0f max=%llu cycles/iteration=%.0f active lanes/iteration=%.1f\n",
+			g[4], g[4] ? static_cast<double>(g[0]) / g[4] : 0.0, g[1], g[4] ? static_cast<double>(g[2]) / g[4] : 0.0, g[3],
+			g[0] ? static_cast<double>(g[2]) / g[0] : 0.0, g[0] ? static_cast<double>(g[5]) / g[0] : 0.0);
+	}
+	fprintf(stderr, "[ckl trail diag] max degree-1/3/4 vertices of a slice=%u, k_trail_walk LDS=%zu bytes\n", max_special, trail_lds_used);
+	fprintf(stderr, "[ckl trail diag, mean per slice] degree-1/3/4 vertices=%.0f corners=%.0f nodes=%.0f starts=%.0f items=%.0f\n", sp, co, m[0], m[3], m[4]);
+}
+
+// a slice whose walk ran out of its scratch arrays has said so in d_slice_err
+void check_walk_errors(ckl_encoder& e, uint32_t ns) {
+	const std::vector<uint32_t> errs = download(e.d_slice_err.p, ns, e.stream);
+	for (uint32_t zi = 0; zi < ns; zi++) if (errs[zi]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: crack walk scratch overflow on z=" + std::to_string(zi));
+}
+
+// Graph -> walk -> finish -> markov -> gather over the session's planes and node counts (graph_pass): capacities,
+// tables, launches, tail.
+CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const CrackRequest& rq) {
 	hipStream_t s = e.stream;
 	const uint32_t ns = static_cast<uint32_t>(sz);
 	const uint64_t nverts = static_cast<uint64_t>(sx + 1) * (sy + 1);
+	const int markov_order = rq.markov_order;
+	const bool reuse_trail = rq.reuse_trail;
+	if (rq.goal == CrackGoal::HISTOGRAM && (!markov_order || rq.model)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: a markov histogram needs an order and no model");
+	CrackResult result;
 	e.d_slice_err.ensure(ns);
 	const bool prezeroed = e.trail_zeroed && !reuse_trail;
 	e.trail_zeroed = false;
 	if (prezeroed) CKL_HIP(hipStreamWaitEvent(s, e.ev_prezero, 0));
 	if (!reuse_trail && !prezeroed) CKL_HIP(hipMemsetAsync(e.d_slice_err.p, 0, ns * sizeof(uint32_t), s));
-	// exact crack edge count per slice: interior pixel pairs that differ (or are equal)
-	const uint64_t interior = static_cast<uint64_t>(sx > 0 ? sx - 1 : 0) * sy + static_cast<uint64_t>(sx) * (sy > 0 ? sy - 1 : 0);
 
-	// capacities from the exact edge counts (codes <= 7 E, chains <= E, stack <= E)
+	// ---- capacities from the exact edge counts (codes <= 7 E, chains <= E, stack <= E)
 	std::vector<uint64_t> cbase(ns), sbase(ns), kbase(ns);
 	std::vector<uint32_t> ccap(ns), scap(ns), kcap(ns), max_steps(ns);
 	std::vector<uint64_t> nbase(ns), cobase(ns), ibase(ns);
@@ -1524,8 +1500,7 @@ void crack_pass(
 	uint32_t max_ncap = 0, max_cocap = 0, max_icap = 0, max_special = 0;
 	bool any = false;
 	for (uint32_t zi = 0; zi < ns; zi++) {
-		const uint64_t differ = static_cast<uint64_t>(e.count_v[zi]) + e.count_h[zi];
-		const uint64_t E = permissible ? interior - differ : differ;
+		const uint64_t E = crack_edges(e, sx, sy, zi, rq.permissible);
 		any = any || E > 0;
 		const uint64_t cc = ((7 * E + 16 + 15) / 16) * 16;      // a multiple of 16: every slice's code arrays start 16-byte aligned (k_finish loads 16 codes at once)
 		if (cc > 0xFFFFFFF0ull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: slice has too many crack edges");
@@ -1546,13 +1521,16 @@ void crack_pass(
 		max_icap = std::max<uint32_t>(max_icap, icap[zi]);
 		max_special = std::max<uint32_t>(max_special, e.count_special[zi]);
 	}
-	if (result) result->any_chain = any;
+	result.any_chain = any;
 	if (g_ht && g_ht->on) {
 		uint32_t over = 0;
 		for (uint32_t zi = 0; zi < ns; zi++) over += e.count_special[zi] > 3584u;
 		fprintf(stderr, "[ckl trail nodes] max special %u, slices above 3584: %u of %u\n", max_special, over, ns);
 	}
 	HT_MARK("c:caps");
+
+	// ---- tables: one packed upload; the arrays and output buffers sized from the capacities (no round trip to
+	// the host before k_finish)
 	UploadPacker tables;
 	tables.add(e.d_cbase, cbase); tables.add(e.d_ccap, ccap);
 	tables.add(e.d_sbase, sbase); tables.add(e.d_scap, scap);
@@ -1564,8 +1542,6 @@ void crack_pass(
 	e.d_chain_order.ensure(ktot); e.d_chain_dst.ensure(ktot); e.d_chain_vstart.ensure(ktot);
 	e.d_n_chains.ensure(ns); e.d_n_raw.ensure(ns); e.d_n_valid.ensure(ns);
 	e.d_payload_len.ensure(ns); e.d_boc_len.ensure(ns);
-
-	// output buffers sized from the capacities (no round trip to the host before k_finish)
 	const int xw = byte_width(static_cast<uint64_t>(sx) + 1), yw = byte_width(static_cast<uint64_t>(sy) + 1);
 	std::vector<uint64_t> pbase(ns), bbase(ns);
 	uint64_t ptot = 0, btot = 0;
@@ -1588,23 +1564,10 @@ void crack_pass(
 	e.codes_capacity = ptot + btot;
 	if (markov_order) CKL_HIP(hipMemsetAsync(e.d_payload.p, 0, ptot + 8, s));
 
-	FinishArgs fa;
-	fa.sx = static_cast<int>(sx); fa.sy = static_cast<int>(sy); fa.xw = xw; fa.yw = yw;
-	fa.markov = markov_order ? 1u : 0u;
-	fa.cbase = e.d_cbase.p; fa.kbase = e.d_kbase.p;
-	fa.n_chains = e.d_n_chains.p; fa.n_raw = e.d_n_raw.p; fa.n_valid = e.d_n_valid.p;
-	fa.cp = e.d_cp.p; fa.chain_node = e.d_chain_node.p; fa.chain_off = e.d_chain_off.p; fa.chain_clen = e.d_chain_clen.p;
-	fa.chain_order = e.d_chain_order.p; fa.chain_dst = e.d_chain_dst.p; fa.chain_vstart = e.d_chain_vstart.p;
-	fa.fcode = e.d_fcode.p; fa.dcode = e.d_dcode.p;
-	fa.pbase = e.d_pbase.p; fa.payload = e.d_payload.p; fa.bbase = e.d_bbase.p; fa.boc = e.d_boc.p;
-	fa.payload_len = e.d_payload_len.p; fa.boc_len = e.d_boc_len.p;
-
-	unsigned long long* ta_dbg = nullptr;
-	size_t trail_lds_used = 0;
+	// ---- launches: the trail over the node graph (ckl_trail.hpp), unless an earlier pass left it
 	DevBuf<unsigned long long> d_tdbg;
-	CKL_HIP(hipEventRecord(e.evk0, s));
+	size_t trail_lds_used = 0;
 	if (!reuse_trail) {
-		// ---- the trail over the node graph (ckl_trail.hpp)
 		e.t_counters.ensure(7 * static_cast<size_t>(ns));
 		if (!prezeroed) CKL_HIP(hipMemsetAsync(e.t_counters.p, 0, 7 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
 		e.t_node_vertex.ensure(ntot); e.t_node_adj.ensure(ntot + 16); e.t_vert2node.ensure(nverts * ns);
@@ -1617,36 +1580,11 @@ void crack_pass(
 		if (!prezeroed) CKL_HIP(hipMemsetAsync(e.t_start_bits.p, 0, static_cast<size_t>(start_words) * ns * sizeof(uint32_t), s));
 		e.t_items.ensure(itot); e.t_item_off.ensure(itot); e.t_chain_item0.ensure(ktot);
 		e.t_events.ensure(itot); e.t_chain_ev0.ensure(ktot); e.t_ev_lnd.ensure(itot); e.t_ev_item.ensure(itot);
-
-		TrailArgs ta;
-		ta.adjm = e.d_adjm.p; ta.adjm_stride = e.adjm_stride; ta.mtx2 = e.mtx2; ta.tiles_x = e.tiles_x; ta.tiles_y = e.tiles_y;
-		ta.planeV = e.d_planes.p; ta.planeH = e.d_planes.p + e.plane_words * ns; ta.row_words = e.row_words; ta.plane_words = e.plane_words;
-		ta.sx = static_cast<uint32_t>(sx); ta.sy = static_cast<uint32_t>(sy); ta.inv = e.graph_permissible ? 0xFFFFFFFFu : 0u;
-		ta.sxe = static_cast<uint32_t>(sx + 1); ta.sye = static_cast<uint32_t>(sy + 1); ta.nverts = static_cast<uint32_t>(nverts);
-		ta.max_steps = e.t_max_steps.p;
-		ta.nbase = e.t_nbase.p; ta.ncap = e.t_ncap.p;
-		ta.n_nodes = e.t_counters.p; ta.n_corners = e.t_counters.p + 2 * ns;
-		ta.n_starts = e.t_counters.p + 3 * ns; ta.n_items = e.t_counters.p + 4 * ns;
-		ta.node_vertex = e.t_node_vertex.p; ta.node_adj = e.t_node_adj.p; ta.vert2node = e.t_vert2node.p;
-		ta.cobase = e.t_cobase.p; ta.cocap = e.t_cocap.p; ta.corner_vertex = e.t_corner_vertex.p;
-		ta.dart_end = e.t_dart_end.p; ta.dart_len = e.t_dart_len.p; ta.dart_minv = e.t_dart_minv.p; ta.dart_minpos = e.t_dart_minpos.p;
-		ta.dart_codes = e.t_dart_codes.p; ta.dart_inline = e.t_dart_inline.p;
-		ta.parent = e.t_parent.p; ta.compmin = e.t_compmin.p;
-		ta.start_bits = e.t_start_bits.p; ta.start_words = start_words; ta.starts = e.t_starts.p;
-		ta.ibase = e.t_ibase.p; ta.icap = e.t_icap.p; ta.items = e.t_items.p; ta.item_off = e.t_item_off.p;
-		ta.sbase = e.d_sbase.p; ta.scap = e.d_scap.p; ta.stack_node = e.d_stack_node.p; ta.stack_item = e.d_stack_code.p;
-		ta.kbase = e.d_kbase.p; ta.kcap = e.d_kcap.p;
-		ta.chain_node = e.d_chain_node.p; ta.chain_item0 = e.t_chain_item0.p; ta.chain_off = e.d_chain_off.p; ta.chain_clen = e.d_chain_clen.p;
-		ta.n_chains = e.d_n_chains.p; ta.n_raw = e.d_n_raw.p; ta.n_valid = e.d_n_valid.p;
-		ta.cbase = e.d_cbase.p; ta.ccap = e.d_ccap.p; ta.cp = e.d_cp.p; ta.slice_err = e.d_slice_err.p;
-
 		e.last_trail_slices = ns;
-		ta.events = e.t_events.p; ta.n_events = e.t_counters.p + 5 * ns; ta.seg_len_sum = e.t_counters.p + 6 * ns; ta.chain_ev0 = e.t_chain_ev0.p; ta.ev_lnd = e.t_ev_lnd.p; ta.ev_item = e.t_ev_item.p;
-		ta.dbg = nullptr;
-		{ const char* env = getenv("CKL_TRAIL_WALK"); ta.walk_plain = (env && !strcmp(env, "plain")) ? 1u : 0u; ta.walk_no_regs = (env && !strcmp(env, "lds")) ? 1u : 0u; }
-		{ const char* env = getenv("CKL_TRAIL_WALK_STACK"); ta.walk_stack_cap = env ? static_cast<uint32_t>(std::max(1, atoi(env))) : 0xFFFFFFFFu; }
-		if (kTuning && getenv("CKL_TRAIL_DIAG")) { d_tdbg.ensure(16); CKL_HIP(hipMemsetAsync(d_tdbg.p, 0, 128, s)); ta.dbg = d_tdbg.p; ta_dbg = d_tdbg.p; }
-		ta.graph_blocks = e.graph_blocks; ta.blk_special = e.t_blk_special.p; ta.blk_corner = e.t_blk_corner.p;
+
+		TrailArgs ta = trail_args(e, sx, sy, ns);
+		const FinishArgs fa = finish_args(e, sx, sy, markov_order);
+		if (kTuning && getenv("CKL_TRAIL_DIAG")) { d_tdbg.ensure(16); CKL_HIP(hipMemsetAsync(d_tdbg.p, 0, 128, s)); ta.dbg = d_tdbg.p; }
 		int max_lds = 0;
 		CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
 		const size_t budget = static_cast<size_t>(max_lds > 1024 ? max_lds - 1024 : 0);
@@ -1668,8 +1606,6 @@ void crack_pass(
 		// (Slice groups on streams of their own, so that one group's parallel stages run beside another's serial
 		// k_trail_walk, measured at C2: 2 groups between -0.17 and +0.1 ms from run to run, 4 and 8 slower — the
 		// DFS wavefronts want their SIMDs to themselves.)
-		ta.z0 = 0;
-		fa.z0 = 0;
 		if (any) {
 			hipLaunchKernelGGL(k_trail_nodes, dim3(e.graph_blocks, ns), dim3(kBlock), 0, s, ta);
 			hipLaunchKernelGGL(k_trail_segments, dim3(dart_blocks, ns), dim3(kBlock), 0, s, ta);
@@ -1684,33 +1620,12 @@ void crack_pass(
 		hipLaunchKernelGGL(k_trail_expand, dim3((max_icap + kExpandChunk * kWaves - 1) / (kExpandChunk * kWaves), ns), dim3(kBlock), 0, s, ta);
 		hipLaunchKernelGGL(k_finish, dim3(ns), dim3(kFinishBlock), 0, s, fa);
 	}
-	CKL_HIP(hipEventRecord(e.evk1, s));
 	HT_MARK("c:enqueue");
-	if (kTuning && getenv("CKL_TRAIL_DIAG")) {
-		std::vector<uint32_t> c = download(e.t_counters.p, 5 * static_cast<size_t>(ns), s);
-		double m[5] = { 0 };
-		for (int k = 0; k < 5; k++) for (uint32_t zi = 0; zi < ns; zi++) m[k] += static_cast<double>(c[static_cast<size_t>(k) * ns + zi]) / ns;
-		double sp = 0, co = 0;
-		for (uint32_t zi = 0; zi < ns; zi++) { sp += static_cast<double>(e.count_special[zi]) / ns; co += static_cast<double>(e.count_corner[zi]) / ns; }
-		if (ta_dbg) {
-			std::vector<unsigned long long> g = download(ta_dbg, 16, s);
-			if (g[11]) fprintf(stderr, "[ckl trail diag, k_trail_walk] mean cycles per slice: table fill=%.0f fill + walk=%.0f\n", static_cast<double>(g[6]) / g[11], static_cast<double>(g[7]) / g[11]);
-			if (g[11]) fprintf(stderr, "[ckl trail diag, k_trail_walk] slices=%llu iterations/slice=%.0f cycles/iteration=%.0f clock=%.2f GHz (cycles / 100 MHz ticks)\n",
-				g[11], static_cast<double>(g[8]) / g[11], g[8] ? static_cast<double>(g[9]) / g[8] : 0.0, g[10] ? static_cast<double>(g[9]) / (g[10] * 10.0) : 0.0);
-			fprintf(stderr, "[ckl trail diag, k_trail_components, mean cycles per slice] union=%.0f component minima=%.0f starts/splits=%.0f bitmap scan=%.0f\n",
-				static_cast<double>(g[12]) / ns, static_cast<double>(g[13]) / ns, static_cast<double>(g[14]) / ns, static_cast<double>(g[15]) / ns);
-			fprintf(stderr, "[ckl trail diag, k_trail_segments] waves=%llu iterations/wave mean=%.1f max=%llu cycles/wave mean=%.0f max=%llu cycles/iteration=%.0f active lanes/iteration=%.1f\n",
-				g[4], g[4] ? static_cast<double>(g[0]) / g[4] : 0.0, g[1], g[4] ? static_cast<double>(g[2]) / g[4] : 0.0, g[3],
-				g[0] ? static_cast<double>(g[2]) / g[0] : 0.0, g[0] ? static_cast<double>(g[5]) / g[0] : 0.0);
-		}
-		fprintf(stderr, "[ckl trail diag] max degree-1/3/4 vertices of a slice=%u, k_trail_walk LDS=%zu bytes\n", max_special, trail_lds_used);
-		fprintf(stderr, "[ckl trail diag, mean per slice] degree-1/3/4 vertices=%.0f corners=%.0f nodes=%.0f starts=%.0f items=%.0f\n", sp, co, m[0], m[3], m[4]);
-	}
+	if (kTuning && getenv("CKL_TRAIL_DIAG")) trail_diag(e, ns, d_tdbg.p, max_special, trail_lds_used);
 
-	// without a markov model nothing stands between k_finish and the final offsets + gather: they are enqueued before the
-	// label side takes the host thread (it is host-synchronous and ends after the trail: the trail's queue used to idle
-	// 0.2 ms until the host came back to launch them)
-	const bool early_tail = !markov_order && result != nullptr;
+	// ---- tail.  Without a markov model nothing stands between k_finish and the final offsets + gather: they are
+	// enqueued before the label side takes the host thread (it is host-synchronous and ends after the trail: the
+	// trail's queue used to idle 0.2 ms until the host came back to launch them)
 	auto enqueue_tail = [&]() {
 		e.d_out_off.ensure(ns);
 		e.d_code_report.ensure(static_cast<size_t>(ns) + 3);
@@ -1719,17 +1634,13 @@ void crack_pass(
 		hipLaunchKernelGGL(k_gather_codes, dim3(ns), dim3(kBlock), 0, s, e.d_boc.p, e.d_bbase.p, e.d_boc_len.p,
 			e.d_payload.p, e.d_pbase.p, e.d_payload_len.p, e.d_out_off.p, e.d_codes_out.p);
 	};
-	if (early_tail) enqueue_tail();
+	if (!markov_order) enqueue_tail();
 	// the label side (other stream, host-synchronous) runs while the trail kernels execute
-	if (overlap) overlap();
+	if (rq.overlap) rq.overlap();
 	HT_MARK("c:overlap");
 
-
 	if (markov_order) {
-		std::vector<uint8_t> model;
-		if (model_in) {
-			model = *model_in;
-		}
+		if (rq.model) result.model = *rq.model;
 		else {
 			const size_t rows = static_cast<size_t>(1) << (2 * markov_order);
 			e.d_hist.ensure(rows * 4);
@@ -1737,37 +1648,24 @@ void crack_pass(
 			const uint32_t hist_lds = (rows * 4 <= 16384) ? static_cast<uint32_t>(rows * 4) : 0u;    // order <= 6: 64 KiB
 			if (hist_lds * 4 > 48 * 1024) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_markov_hist), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hist_lds * 4)));
 			hipLaunchKernelGGL(k_markov_hist, dim3(ns), dim3(kBlock), hist_lds * sizeof(uint32_t), s, e.d_dcode.p, e.d_cbase.p, e.d_n_valid.p, markov_order, e.d_hist.p, hist_lds);
-			std::vector<uint32_t> hist = download(e.d_hist.p, rows * 4, s);
-			if (hist_out) *hist_out = hist;
-			if (hist_only) {
-				std::vector<uint32_t> errs = download(e.d_slice_err.p, ns, s);
-				for (uint32_t zi = 0; zi < ns; zi++) if (errs[zi]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: crack walk scratch overflow on z=" + std::to_string(zi));
-				return;
-			}
-			model = markov_stats_to_model(hist.data(), rows);
+			result.hist = download(e.d_hist.p, rows * 4, s);
+			if (rq.goal == CrackGoal::HISTOGRAM) { check_walk_errors(e, ns); return result; }
+			result.model = markov_stats_to_model(result.hist.data(), rows);
 		}
-		if (model_out) *model_out = model;
-		upload(e.d_model, model, s);
+		upload(e.d_model, result.model, s);
 		hipLaunchKernelGGL(k_markov_pack, dim3(ns), dim3(kBlock), 0, s, e.d_dcode.p, e.d_cbase.p, e.d_n_valid.p, markov_order,
 			e.d_model.p, e.d_pbase.p, e.d_payload.p, e.d_payload_len.p);
+		// final offsets on the device, the gather behind them
+		enqueue_tail();
 	}
-	if (!result) { CKL_HIP(hipStreamSynchronize(s)); return; }
-
-	// final offsets on the device, the gather behind them, one small report back (lengths for the
-	// z-index, total, error bits): a single wait before the codes are copied out
-	if (!early_tail) enqueue_tail();
+	// one small report back (lengths for the z-index, total, error bits): a single wait before the codes are copied out
 	HT_MARK("c:finish_enq");
-	std::vector<uint32_t> report = download(e.d_code_report.p, static_cast<size_t>(ns) + 3, s);
+	const std::vector<uint32_t> report = download(e.d_code_report.p, static_cast<size_t>(ns) + 3, s);
 	HT_MARK("c:finish_wait");
-	if (report[ns + 2]) {
-		std::vector<uint32_t> errs = download(e.d_slice_err.p, ns, s);
-		for (uint32_t zi = 0; zi < ns; zi++) {
-			if (errs[zi]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: crack walk scratch overflow on z=" + std::to_string(zi));
-		}
-	}
-	result->code_len.assign(report.begin(), report.begin() + ns);
-	const uint64_t otot = static_cast<uint64_t>(report[ns]) | (static_cast<uint64_t>(report[ns + 1]) << 32);
-	result->total = otot;
+	if (report[ns + 2]) check_walk_errors(e, ns);
+	result.code_len.assign(report.begin(), report.begin() + ns);
+	result.total = static_cast<uint64_t>(report[ns]) | (static_cast<uint64_t>(report[ns + 1]) << 32);
+	return result;
 }
 
 struct FlatResult {
@@ -1801,6 +1699,16 @@ void ensure_geom_table(ckl_encoder& e, uint64_t sxy) {
 	e.g_table_pixels = sxy;
 }
 
+// the run kernels' view of the session's run tables (ckl_runs.hpp)
+RunArrays flat_arrays(const ckl_encoder& e) {
+	RunArrays ra;
+	ra.word_base = e.d_word_base.p; ra.rbase = e.d_rbase.p; ra.rcap = e.d_rcap.p;
+	ra.parent = e.d_parent.p; ra.run_start = e.d_run_start.p; ra.run_cc = e.d_run_cc.p;
+	ra.nruns = e.d_nruns.p; ra.ncomp = e.d_ncomp.p; ra.slice_err = e.d_slice_err2.p;
+	ra.comp_pix = e.d_comp_pix.p;
+	return ra;
+}
+
 // encode_flat per-slice part (labels.hpp:56-88) on runs of the label planes: components
 // and their crc32c.  Enqueued on the label stream right after the planes exist; the
 // results are collected (flat_collect) while the crack trail runs on the other stream.
@@ -1822,7 +1730,6 @@ void flat_enqueue(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
 		rbase[zi] = rtot; rcap[zi] = static_cast<uint32_t>(runs); rtot += runs;
 		max_rcap = std::max<uint32_t>(max_rcap, static_cast<uint32_t>(runs));
 	}
-	e.flat_max_rcap = max_rcap;
 	upload(e.d_rbase, rbase, s); upload(e.d_rcap, rcap, s);
 	e.d_word_base.ensure(e.plane_words * ns);
 	e.d_parent.ensure(rtot); e.d_run_start.ensure(rtot); e.d_run_cc.ensure(rtot); e.d_comp_pix.ensure(rtot);
@@ -1835,15 +1742,11 @@ void flat_enqueue(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
 	CKL_HIP(hipMemsetAsync(e.d_slice_err2.p, 0, ns * sizeof(uint32_t), s));
 
 	RunGeom g;
-	g.planeV = e.d_planes.p; g.planeH = e.d_planes.p + e.plane_words * ns;
+	g.planeV = plane_v(e); g.planeH = plane_h(e, ns);
 	g.row_words = e.row_words; g.plane_words = e.plane_words;
 	g.flip = 1u;   // a set bit (labels differ) is a break, whatever the stream's crack format
 	g.sx = static_cast<uint32_t>(sx); g.sy = static_cast<uint32_t>(sy);
-	RunArrays ra;
-	ra.word_base = e.d_word_base.p; ra.rbase = e.d_rbase.p; ra.rcap = e.d_rcap.p;
-	ra.parent = e.d_parent.p; ra.run_start = e.d_run_start.p; ra.run_cc = e.d_run_cc.p;
-	ra.nruns = e.d_nruns.p; ra.ncomp = e.d_ncomp.p; ra.slice_err = e.d_slice_err2.p;
-	ra.comp_pix = e.d_comp_pix.p;
+	const RunArrays ra = flat_arrays(e);
 	hipLaunchKernelGGL(k_run_index, dim3(ns), dim3(kIndexBlock), 0, s, g, ra);
 	launch_run_union(s, ns, g, ra);
 	ResolveScratch rs;
@@ -1861,22 +1764,11 @@ void flat_collect(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	hipStream_t s = e.stream2;
 	const uint32_t ns = static_cast<uint32_t>(sz);
 	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	std::vector<uint32_t> acc, idbits, errs;
-	if (e.d_ncomp.p == e.d_flat_report.p && e.d_flat_report.p) {      // laid out by flat_enqueue: one transfer
-		const std::vector<uint32_t> rep = download(e.d_flat_report.p, 4 * static_cast<size_t>(ns), s);
-		out.ncomp.assign(rep.begin(), rep.begin() + ns);
-		acc.assign(rep.begin() + ns, rep.begin() + 2 * static_cast<size_t>(ns));
-		idbits.assign(rep.begin() + 2 * static_cast<size_t>(ns), rep.begin() + 3 * static_cast<size_t>(ns));
-		errs.assign(rep.begin() + 3 * static_cast<size_t>(ns), rep.end());
-		HT_MARK("f:wait");
-	}
-	else {
-		out.ncomp = download(e.d_ncomp.p, ns, s);
-		HT_MARK("f:wait");
-		acc = download(e.d_crc_acc.p, ns, s);
-		idbits = download(e.d_idbits.p, ns, s);
-		errs = download(e.d_slice_err2.p, ns, s);
-	}
+	// laid out by flat_enqueue: ncomp | crc_acc | idbits | slice_err2, one transfer
+	const std::vector<uint32_t> rep = download(e.d_flat_report.p, 4 * static_cast<size_t>(ns), s);
+	const uint32_t *acc = rep.data() + ns, *idbits = rep.data() + 2 * static_cast<size_t>(ns), *errs = rep.data() + 3 * static_cast<size_t>(ns);
+	out.ncomp.assign(rep.begin(), rep.begin() + ns);
+	HT_MARK("f:wait");
 	for (uint32_t zi = 0; zi < ns; zi++) if (errs[zi]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: run table overflow on z=" + std::to_string(zi));
 	const uint32_t init_term = gf_mul(0xFFFFFFFFu, gf_xpow(32ull * sxy));
 	out.crcs.resize(ns);
@@ -1891,452 +1783,13 @@ void flat_collect(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	for (uint32_t zi = 0; zi < ns; zi++) { comp_off[zi] = total; total += out.ncomp[zi]; }
 	upload(e.d_comp_off, comp_off, s);
 	e.d_mapping.ensure(total + 1);
-	RunArrays ra;
-	ra.word_base = e.d_word_base.p; ra.rbase = e.d_rbase.p; ra.rcap = e.d_rcap.p;
-	ra.parent = e.d_parent.p; ra.run_start = e.d_run_start.p; ra.run_cc = e.d_run_cc.p;
-	ra.nruns = e.d_nruns.p; ra.ncomp = e.d_ncomp.p; ra.slice_err = e.d_slice_err2.p;
-	ra.comp_pix = e.d_comp_pix.p;
+	const RunArrays ra = flat_arrays(e);
 	uint32_t max_ncomp = 1;
 	for (uint32_t zi = 0; zi < ns; zi++) max_ncomp = std::max(max_ncomp, out.ncomp[zi]);
 	hipLaunchKernelGGL(k_mapping_comps<LABEL>, dim3((max_ncomp + kBlock - 1) / kBlock, ns), dim3(kBlock), 0, s,
 		labels, ra, sxy, e.d_comp_off.p, e.d_mapping.p);
 	CKL_HIP(hipStreamSynchronize(s));   // comp_off (pageable) must be consumed before it goes out of scope
 	out.total = total;
-}
-
-// the labels with the key of their first column run (the order they enter `pinsets`, src/pins.hpp:126-163), from the
-// components' labels and first runs on the device
-// The labels with their first column runs (k_pin_label_first / _list) in two steps: the kernels, enqueued as soon as
-// first_any is final (behind the first column pass), and the collection of the two short lists — on a stream of its
-// own, so that it does not queue behind the passes that follow on the label stream.
-struct PinLabelLists {
-	DevBuf<uint64_t> d_tab;
-	DevBuf<uint32_t> d_count;
-	uint32_t slots = 0;
-	hipEvent_t ready = nullptr;
-	~PinLabelLists() { if (ready) (void)hipEventDestroy(ready); }
-};
-void pin_label_table_enqueue(ckl_encoder& e, const uint64_t* comp_label, const uint64_t* first_any_dev, uint64_t N, PinLabelLists& t) {
-	hipStream_t s = e.stream2;
-	if (N > (1ull << 30)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components for pin labels");
-	uint32_t slots = 1024;
-	while (slots < 2 * N) slots <<= 1;
-	t.slots = slots;
-	t.d_tab.ensure(4ull * slots + 1);      // keys | values | label list | first list, + the all-ones label's minimum
-	t.d_count.ensure(1);
-	CKL_HIP(hipMemsetAsync(t.d_tab.p, 0xFF, (2ull * slots) * sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(t.d_tab.p + 4ull * slots, 0xFF, sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(t.d_count.p, 0, sizeof(uint32_t), s));
-	unsigned long long* tab = reinterpret_cast<unsigned long long*>(t.d_tab.p);
-	hipLaunchKernelGGL(k_pin_label_first, dim3(static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock)), dim3(kPinBlock), 0, s,
-		reinterpret_cast<const unsigned long long*>(comp_label), reinterpret_cast<const unsigned long long*>(first_any_dev), N, tab, tab + slots, slots - 1u, tab + 4ull * slots);
-	hipLaunchKernelGGL(k_pin_label_list, dim3((slots + kPinBlock - 1) / kPinBlock), dim3(kPinBlock), 0, s, tab, tab + slots, slots, t.d_count.p, tab + 2ull * slots, tab + 3ull * slots);
-	if (!t.ready) CKL_HIP(hipEventCreateWithFlags(&t.ready, hipEventDisableTiming));
-	CKL_HIP(hipEventRecord(t.ready, s));
-}
-void pin_label_table_collect(ckl_encoder& e, PinLabelLists& t, PinCandidates& pc) {
-	if (!e.stream_tab) CKL_HIP(hipStreamCreateWithFlags(&e.stream_tab, hipStreamNonBlocking));
-	hipStream_t s = e.stream_tab;
-	CKL_HIP(hipStreamWaitEvent(s, t.ready, 0));
-	const uint32_t nl = download(t.d_count.p, 1, s)[0];
-	pc.label_value = download(t.d_tab.p + 2ull * t.slots, nl, s);
-	pc.label_first = download(t.d_tab.p + 3ull * t.slots, nl, s);
-	const uint64_t max_first = download(t.d_tab.p + 4ull * t.slots, 1, s)[0];
-	if (max_first != kPinNoKey) { pc.label_value.push_back(kPinNoKey); pc.label_first.push_back(max_first); }
-}
-void pin_label_table(ckl_encoder& e, const uint64_t* comp_label, const uint64_t* first_any_dev, uint64_t N, PinCandidates& pc) {
-	PinLabelLists t;
-	pin_label_table_enqueue(e, comp_label, first_any_dev, N, t);
-	pin_label_table_collect(e, t, pc);
-}
-
-// extract_columns + add_pin (src/pins.hpp:95-163) over the rows of `v`: the kept runs marked in v.mark
-template <typename LABEL>
-void pin_dedup_pass(ckl_encoder& e, const LABEL* labels, const PinVolume& v) {
-	hipStream_t s = e.stream2;
-	const bool by_thread = getenv("CKL_PINS_ROW_THREADS") != nullptr;      // testing: the general kernel on small volumes
-	if (v.sz <= 1024u && !by_thread) {
-		// a wavefront per row, label tables in registers
-		const dim3 wgrid((v.sy + kPinWaves - 1) / kPinWaves), wblock(64 * kPinWaves);
-		// four columns per load where the rows allow it
-		// (2048 x 2048 x 256 uint32, the kernel alone: 19.9 ms with one column per load, 9.2 with four, 9.3 / 9.6 with 8 / 16)
-		const bool groups = v.sx % 4u == 0 && (reinterpret_cast<uintptr_t>(labels) % (4 * sizeof(LABEL))) == 0 && !getenv("CKL_PINS_COLUMN_LOADS");
-#define CKL_DEDUP(K) do { \
-			if (groups) hipLaunchKernelGGL((k_pin_dedup_wave<LABEL, K, 4>), wgrid, wblock, 0, s, labels, v); \
-			else hipLaunchKernelGGL((k_pin_dedup_wave<LABEL, K, 1>), wgrid, wblock, 0, s, labels, v); \
-		} while (0)
-		if (v.sz <= 64u) CKL_DEDUP(1);
-		else if (v.sz <= 128u) CKL_DEDUP(2);
-		else if (v.sz <= 256u) CKL_DEDUP(4);
-		else if (v.sz <= 512u) CKL_DEDUP(8);
-		else CKL_DEDUP(16);
-#undef CKL_DEDUP
-	}
-	else {
-		// taller volumes: a thread per row with its label tables in global memory
-		uint32_t cap = 16;
-		while (cap < 2u * v.sz) cap <<= 1;
-		const uint64_t slots = 2ull * cap * v.sy;
-		e.d_pin_tables.ensure(slots * sizeof(PinSlot));
-		CKL_HIP(hipMemsetAsync(e.d_pin_tables.p, 0, slots * sizeof(PinSlot), s));
-		hipLaunchKernelGGL(k_pin_dedup<LABEL>, dim3((v.sy + kPinRowBlock - 1) / kPinRowBlock), dim3(kPinRowBlock), 0, s,
-			labels, v, reinterpret_cast<PinSlot*>(e.d_pin_tables.p), cap);
-	}
-
-}
-
-// extract_columns / compute_multiverse / the component -> pin choice of find_suboptimal_pins
-// (src/pins.hpp:95-198, 300-346) as device passes over the resident label volume and
-// the component id volume (ckl_pins_dev.hpp); only per-component facts and the chosen pins are copied out.
-template <typename LABEL>
-void pin_passes_device(
-	ckl_encoder& e, const LABEL* labels, const uint32_t* cc /* device: component id of every voxel */,
-	int64_t sx_, int64_t sy_, int64_t sz_, uint64_t N, PinVolume& v, unsigned long long*& choice, const uint64_t*& first_any,
-	const std::function<void(const uint64_t*)>& first_any_final = std::function<void(const uint64_t*)>()      // called (with first_any) once the pass that completes it is enqueued
-) {
-	hipStream_t s = e.stream2;
-	v = PinVolume();
-	v.sx = static_cast<uint32_t>(sx_); v.sy = static_cast<uint32_t>(sy_); v.sz = static_cast<uint32_t>(sz_);
-	v.sxy = static_cast<uint64_t>(v.sx) * v.sy;
-	const uint64_t voxels = v.sxy * v.sz;
-	if (v.sz > 65535u) throw Error(CKL_ERR_ARG, "crackle_amd: pin labels need at most 65535 slices");      // the kept marks hold depth + 1 in 16 bits
-	const uint64_t mark_words = (voxels + 1) / 2;
-	e.d_pin_kept.ensure(mark_words);
-	CKL_HIP(hipMemsetAsync(e.d_pin_kept.p, 0, mark_words * sizeof(uint32_t), s));
-	v.cc = cc; v.mark = reinterpret_cast<uint16_t*>(e.d_pin_kept.p);
-
-	pin_dedup_pass<LABEL>(e, labels, v);
-
-	e.d_pin_u64.ensure(4 * N + 1);
-	e.d_pin_u32.ensure(N + 1);
-	PinComponentArrays a;
-	a.first_any = reinterpret_cast<unsigned long long*>(e.d_pin_u64.p);
-	a.first_kept = a.first_any + N;
-	a.best = a.first_kept + N;
-	choice = a.best + N;
-	first_any = reinterpret_cast<const uint64_t*>(a.first_any);
-	a.first_depth = e.d_pin_u32.p;
-	CKL_HIP(hipMemsetAsync(a.first_any, 0xFF, 2 * N * sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(a.best, 0, N * sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(a.first_depth, 0, N * sizeof(uint32_t), s));
-	const dim3 cgrid((v.sx + kPinBlock - 1) / kPinBlock, v.sy);
-	hipLaunchKernelGGL((k_pin_columns<LABEL, 0>), cgrid, dim3(kPinBlock), 0, s, labels, v, a);
-	if (first_any_final) first_any_final(first_any);
-	hipLaunchKernelGGL((k_pin_extent<LABEL, true>), dim3(static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock)), dim3(kPinBlock), 0, s,
-		labels, v, a.first_kept, static_cast<uint32_t>(N), a.first_depth);
-	hipLaunchKernelGGL((k_pin_columns<LABEL, 2>), cgrid, dim3(kPinBlock), 0, s, labels, v, a);
-	hipLaunchKernelGGL(k_pin_choice, dim3(static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock)), dim3(kPinBlock), 0, s, a, N, choice);
-}
-
-// `passes`: the PinVolume / choice / first_any of a pin_passes_device call that has run already (else it runs here)
-template <typename LABEL>
-PinCandidates pin_candidates_device(
-	ckl_encoder& e, const LABEL* labels, const uint32_t* cc /* device: component id of every voxel */,
-	const uint64_t* comp_label /* device: label of every component */, int64_t sx_, int64_t sy_, int64_t sz_, uint64_t N,
-	const PinVolume* passes = nullptr, unsigned long long* choice = nullptr, const uint64_t* first_any_dev = nullptr
-) {
-	hipStream_t s = e.stream2;
-	PinVolume v;
-	if (passes) v = *passes;
-	else pin_passes_device<LABEL>(e, labels, cc, sx_, sy_, sz_, N, v, choice, first_any_dev);
-	struct { const unsigned long long* first_any; } a = { reinterpret_cast<const unsigned long long*>(first_any_dev) };
-
-	CKL_HIP(hipStreamSynchronize(s));
-	HT_MARK("p:passes");
-	PinCandidates pc;
-	pc.comp_label = download(comp_label, N, s);
-	pc.comp_first = download(reinterpret_cast<const uint64_t*>(a.first_any), N, s);
-	std::vector<uint64_t> chosen = download(reinterpret_cast<const uint64_t*>(choice), N, s);
-
-	HT_MARK("p:d2h");
-	if (N >= kPinNone) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many pins");
-	// The pins: by default every component's pin is an entry of its own (the same run may appear several
-	// times: a pin is taken at most once, since taking it removes every component that maps to it) and no
-	// sorting is needed.  The ids of a run are then stored once per component that chose it — volumes
-	// with long z-runs could reach N x sz ids — so when the entries' ids pass a budget the chosen runs
-	// are reduced to the distinct ones first (a sort of the keys on the host).
-	uint32_t P = static_cast<uint32_t>(N);
-	std::vector<uint64_t> pin_key(chosen);      // key of pin p (identity mapping: the component's choice)
-	pc.comp_pin.assign(N, kPinNone);
-	for (uint32_t c = 0; c < P; c++) if (chosen[c] != kPinNoKey) pc.comp_pin[c] = c;
-	{
-		DevBuf<uint32_t> d_ze0;
-		d_ze0.ensure(P);
-		CKL_HIP(hipMemsetAsync(d_ze0.p, 0, static_cast<size_t>(P) * sizeof(uint32_t), s));
-		hipLaunchKernelGGL((k_pin_extent<LABEL, false>), dim3((P + kPinBlock - 1) / kPinBlock), dim3(kPinBlock), 0, s, labels, v, choice, P, d_ze0.p);
-		pc.pin_ze = download(d_ze0.p, P, s);
-	}
-	uint64_t id_total = 0;
-	for (uint32_t c = 0; c < P; c++) if (chosen[c] != kPinNoKey) id_total += pc.pin_ze[c] - static_cast<uint32_t>(chosen[c] % v.sz) + 1u;
-	uint64_t id_budget = 1ull << 26;      // 256 MiB of ids
-	if (const char* env = getenv("CKL_PIN_IDS_BUDGET")) id_budget = static_cast<uint64_t>(std::max(0, atoi(env)));      // testing: forces the distinct-pin path
-	DevBuf<unsigned long long> d_key2;
-	const unsigned long long* key_dev = choice;
-	if (id_total > id_budget) {
-		std::vector<uint32_t> order;
-		order.reserve(P);
-		for (uint32_t c = 0; c < P; c++) if (chosen[c] != kPinNoKey) order.push_back(c);
-		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return chosen[a] != chosen[b] ? chosen[a] < chosen[b] : a < b; });
-		std::vector<uint64_t> keys2;
-		std::vector<uint32_t> ze2;
-		for (size_t i = 0; i < order.size(); i++) {
-			const uint32_t c = order[i];
-			if (i == 0 || chosen[c] != chosen[order[i - 1]]) { keys2.push_back(chosen[c]); ze2.push_back(pc.pin_ze[c]); }
-			pc.comp_pin[c] = static_cast<uint32_t>(keys2.size() - 1);
-		}
-		pin_key.swap(keys2);
-		pc.pin_ze.swap(ze2);
-		P = static_cast<uint32_t>(pin_key.size());
-		d_key2.ensure(std::max<size_t>(P, 1));
-		if (P) CKL_HIP(hipMemcpyAsync(d_key2.p, pin_key.data(), static_cast<size_t>(P) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-		key_dev = d_key2.p;
-	}
-	pc.pin_x.assign(P, 0); pc.pin_y.assign(P, 0); pc.pin_zs.assign(P, 0);
-	for (uint32_t p = 0; p < P; p++) {
-		if (pin_key[p] == kPinNoKey) continue;
-		const uint64_t col = pin_key[p] / v.sz;
-		pc.pin_zs[p] = static_cast<uint32_t>(pin_key[p] % v.sz);
-		pc.pin_x[p] = static_cast<uint32_t>(col % v.sx);
-		pc.pin_y[p] = static_cast<uint32_t>(col / v.sx);
-	}
-	HT_MARK("p:keys");
-	pc.pin_ids_off.assign(static_cast<size_t>(P) + 1, 0);
-	{
-		DevBuf<uint64_t> d_off;
-		DevBuf<uint32_t> d_ze, d_ids;
-		for (uint32_t p = 0; p < P; p++) {
-			if (pin_key[p] == kPinNoKey) { pc.pin_ze[p] = pc.pin_zs[p]; pc.pin_ids_off[p + 1] = pc.pin_ids_off[p]; }
-			else pc.pin_ids_off[p + 1] = pc.pin_ids_off[p] + (pc.pin_ze[p] - pc.pin_zs[p] + 1u);
-		}
-		upload(d_off, pc.pin_ids_off, s);
-		upload(d_ze, pc.pin_ze, s);
-		d_ids.ensure(pc.pin_ids_off[P] + 1);
-		if (P) hipLaunchKernelGGL(k_pin_ids, dim3((P + kPinBlock - 1) / kPinBlock), dim3(kPinBlock), 0, s, v, key_dev, d_ze.p, d_off.p, P, d_ids.p);
-		pc.pin_ids = download(d_ids.p, pc.pin_ids_off[P], s);
-	}
-	pin_label_table(e, comp_label, reinterpret_cast<const uint64_t*>(a.first_any), N, pc);
-	HT_MARK("p:ids");
-	return pc;
-}
-
-
-// ---- the pin stage sharded by ROWS (config C4 on several GPUs) -----------------------------------------------------
-// Candidate pins are z-runs per (x, y) column over the WHOLE volume, so a z-slab cannot find them; a slab of rows
-// [y0, y0 + rows) of every slice can: extract_columns / add_pin compare a run only with the label's last pin in the
-// previous column of the same row (src/pins.hpp:134-160), so rows are independent, and what is kept per COMPONENT
-// (a component lies in one slice but spans rows) is an extremum over its voxels:
-//   first_any   smallest key of a run starting in the component                          -> minimum over the ranks
-//   first_kept  smallest key of a kept run containing it, with that run's depth          -> minimum of key << 16 | depth
-//   best        1 + largest key of a kept run deeper than the first kept one (0: none)   -> maximum, once every rank knows
-//                                                                                           the first run's depth
-//   z_e + 1     last slice of the chosen run, known to the rank that holds its row        -> maximum (0 elsewhere)
-//   ids         component ids along the chosen run, likewise                              -> maximum (0 elsewhere)
-// The caller (crackle_amd/distributed.py) holds the arrays in its device memory, reduces them over its process group
-// between the calls (RCCL all_reduce of N-entry arrays: 13 MB each for C4's 1.6 M components) and hands the reduced
-// arrays back; rank 0 finally runs the ordered cover (ckl_pins_rows_section).  Keys name columns of the whole volume.
-template <typename LABEL>
-PinVolume pin_rows_volume(ckl_encoder& e, const uint32_t* cc, int64_t sx, int64_t rows, int64_t sz, int64_t y0, bool fresh_marks) {
-	PinVolume v;
-	v.sx = static_cast<uint32_t>(sx); v.sy = static_cast<uint32_t>(rows); v.sz = static_cast<uint32_t>(sz);
-	v.sxy = static_cast<uint64_t>(v.sx) * v.sy;
-	v.key_col0 = static_cast<uint64_t>(y0) * v.sx;
-	if (v.sz > 65535u) throw Error(CKL_ERR_ARG, "crackle_amd: pin labels need at most 65535 slices");
-	const uint64_t mark_words = (v.sxy * v.sz + 1) / 2;
-	if (fresh_marks) {
-		e.d_pin_kept.ensure(mark_words);
-		CKL_HIP(hipMemsetAsync(e.d_pin_kept.p, 0, mark_words * sizeof(uint32_t), e.stream2));
-	}
-	else if (!e.d_pin_kept.p || e.d_pin_kept.n < mark_words) throw Error(CKL_ERR_ARG, "crackle_amd: ckl_pins_rows_first has to run first");
-	v.cc = cc; v.mark = reinterpret_cast<uint16_t*>(e.d_pin_kept.p);
-	return v;
-}
-
-template <typename LABEL>
-void pins_rows_first(ckl_encoder& e, const LABEL* labels, const uint32_t* cc, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t N,
-	uint64_t* first_any, uint64_t* first_kept_packed, uint64_t* comp_label) {
-	hipStream_t s = e.stream2;
-	const PinVolume v = pin_rows_volume<LABEL>(e, cc, sx, rows, sz, y0, true);
-	const uint32_t nb = static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock);
-	// the label of every component that shows in these rows (0 elsewhere: the ranks' arrays merge by maximum)
-	e.d_slice_err2.ensure(1);
-	CKL_HIP(hipMemsetAsync(comp_label, 0, N * sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(e.d_slice_err2.p, 0, sizeof(uint32_t), s));
-	const uint64_t voxels = v.sxy * v.sz;
-	const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((voxels + kPinBlock - 1) / kPinBlock, 0x7FFFFFFFull));
-	hipLaunchKernelGGL(k_pin_component_labels<LABEL>, dim3(blocks), dim3(kPinBlock), 0, s, labels, cc, voxels, v.sx, N, reinterpret_cast<unsigned long long*>(comp_label), e.d_slice_err2.p);
-	pin_dedup_pass<LABEL>(e, labels, v);
-	e.d_pin_u64.ensure(N + 1);
-	e.d_pin_u32.ensure(N + 1);
-	PinComponentArrays a;
-	a.first_any = reinterpret_cast<unsigned long long*>(first_any);
-	a.first_kept = reinterpret_cast<unsigned long long*>(e.d_pin_u64.p);
-	a.best = nullptr;
-	a.first_depth = e.d_pin_u32.p;
-	CKL_HIP(hipMemsetAsync(a.first_any, 0xFF, N * sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(a.first_kept, 0xFF, N * sizeof(uint64_t), s));
-	CKL_HIP(hipMemsetAsync(a.first_depth, 0, N * sizeof(uint32_t), s));
-	const dim3 cgrid((v.sx + kPinBlock - 1) / kPinBlock, v.sy);
-	hipLaunchKernelGGL((k_pin_columns<LABEL, 0>), cgrid, dim3(kPinBlock), 0, s, labels, v, a);
-	hipLaunchKernelGGL((k_pin_extent<LABEL, true>), dim3(nb), dim3(kPinBlock), 0, s, labels, v, a.first_kept, static_cast<uint32_t>(N), a.first_depth);
-	hipLaunchKernelGGL(k_pin_pack_first, dim3(nb), dim3(kPinBlock), 0, s, a.first_kept, a.first_depth, N, reinterpret_cast<unsigned long long*>(first_kept_packed));
-	if (download(e.d_slice_err2.p, 1, s)[0]) throw Error(CKL_ERR_ARG, "crackle_amd: component id out of range");
-}
-
-template <typename LABEL>
-void pins_rows_best(ckl_encoder& e, const LABEL* labels, const uint32_t* cc, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t N,
-	const uint64_t* first_kept_packed, uint64_t* best) {
-	hipStream_t s = e.stream2;
-	const PinVolume v = pin_rows_volume<LABEL>(e, cc, sx, rows, sz, y0, false);
-	const uint32_t nb = static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock);
-	e.d_pin_u64.ensure(N + 1);
-	e.d_pin_u32.ensure(N + 1);
-	PinComponentArrays a;
-	a.first_any = nullptr;
-	a.first_kept = reinterpret_cast<unsigned long long*>(e.d_pin_u64.p);
-	a.best = reinterpret_cast<unsigned long long*>(best);
-	a.first_depth = e.d_pin_u32.p;
-	hipLaunchKernelGGL(k_pin_unpack_first, dim3(nb), dim3(kPinBlock), 0, s, reinterpret_cast<const unsigned long long*>(first_kept_packed), N, a.first_kept, a.first_depth);
-	CKL_HIP(hipMemsetAsync(a.best, 0, N * sizeof(uint64_t), s));
-	const dim3 cgrid((v.sx + kPinBlock - 1) / kPinBlock, v.sy);
-	hipLaunchKernelGGL((k_pin_columns<LABEL, 2>), cgrid, dim3(kPinBlock), 0, s, labels, v, a);
-	CKL_HIP(hipStreamSynchronize(s));
-}
-
-template <typename LABEL>
-void pins_rows_extent(ckl_encoder& e, const LABEL* labels, const uint32_t* cc, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t N,
-	const uint64_t* first_kept_packed, const uint64_t* best, uint64_t* choice, uint32_t* ze_plus1) {
-	hipStream_t s = e.stream2;
-	const PinVolume v = pin_rows_volume<LABEL>(e, cc, sx, rows, sz, y0, false);
-	const uint32_t nb = static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock);
-	e.d_pin_u64.ensure(N + 1);
-	e.d_pin_u32.ensure(N + 1);
-	PinComponentArrays a;
-	a.first_any = nullptr;
-	a.first_kept = reinterpret_cast<unsigned long long*>(e.d_pin_u64.p);
-	a.best = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(best));
-	a.first_depth = e.d_pin_u32.p;
-	hipLaunchKernelGGL(k_pin_unpack_first, dim3(nb), dim3(kPinBlock), 0, s, reinterpret_cast<const unsigned long long*>(first_kept_packed), N, a.first_kept, a.first_depth);
-	hipLaunchKernelGGL(k_pin_choice, dim3(nb), dim3(kPinBlock), 0, s, a, N, reinterpret_cast<unsigned long long*>(choice));
-	CKL_HIP(hipMemsetAsync(ze_plus1, 0, N * sizeof(uint32_t), s));
-	hipLaunchKernelGGL((k_pin_extent<LABEL, false, true>), dim3(nb), dim3(kPinBlock), 0, s, labels, v, reinterpret_cast<const unsigned long long*>(choice), static_cast<uint32_t>(N), ze_plus1);
-	CKL_HIP(hipStreamSynchronize(s));
-}
-
-// The pin label section from the per-component arrays in device memory (every chosen pin an entry of its own:
-// pin c is component c's choice): the arrays come to the host in ONE pinned block (host_out_alloc: cached between
-// calls), the per-pin bookkeeping runs on the worker threads, pins_cover_host reads the block in place.
-// choice[c]: key of the chosen run or kPinNoKey; ze_plus1[c]: its last slice + 1; offsets: N + 1 prefix sums of the
-// runs' lengths; ids: the component ids along the runs.
-std::vector<uint8_t> pins_section_from_device(
-	ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, uint64_t N, const std::vector<uint32_t>& nc,
-	const uint64_t* d_comp_label, const uint64_t* d_first_any, const uint64_t* d_choice, const uint32_t* d_ze_plus1, const uint64_t* d_offsets, const uint32_t* d_ids,
-	int stored_width, bool auto_bgcolor, int64_t manual_bgcolor, const PinLabelTable* table = nullptr
-) {
-	hipStream_t s = e.stream2;
-	PinCandidates pc;
-	if (!table) pin_label_table(e, d_comp_label, d_first_any, N, pc);      // the labels with their first runs: a few downloads of its own
-	const uint64_t total = download(d_offsets + N, 1, s)[0];
-	auto up64 = [](uint64_t b) { return (b + 63) & ~static_cast<uint64_t>(63); };
-	const uint64_t o_label = 0, o_choice = o_label + up64(N * 8), o_off = o_choice + up64(N * 8), o_ze = o_off + up64((N + 1) * 8), o_ids = o_ze + up64(N * 4);
-	const uint64_t o_pins = o_ids + up64(std::max<uint64_t>(total, 1) * 4);      // comp_pin, pin_x, pin_y, pin_zs, pin_ze: written by the host, in the same cached block (no page faults, no zero fill)
-	const uint64_t bytes = o_pins + 5 * up64(N * 4);
-	struct Block { uint8_t* p = nullptr; hipStream_t s = nullptr; ~Block() { if (p) { (void)hipStreamSynchronize(s); host_out_free(p); } } } blk;      // (copies may still be on their way when an error unwinds)
-	blk.s = s;
-	blk.p = static_cast<uint8_t*>(host_out_alloc(bytes));
-	CKL_HIP(hipMemcpyAsync(blk.p + o_label, d_comp_label, N * 8, hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipMemcpyAsync(blk.p + o_choice, d_choice, N * 8, hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipMemcpyAsync(blk.p + o_off, d_offsets, (N + 1) * 8, hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipMemcpyAsync(blk.p + o_ze, d_ze_plus1, N * 4, hipMemcpyDeviceToHost, s));
-	if (total) CKL_HIP(hipMemcpyAsync(blk.p + o_ids, d_ids, total * 4, hipMemcpyDeviceToHost, s));
-	uint32_t* const h_comp_pin = reinterpret_cast<uint32_t*>(blk.p + o_pins);
-	uint32_t* const h_x = reinterpret_cast<uint32_t*>(blk.p + o_pins + up64(N * 4));
-	uint32_t* const h_y = reinterpret_cast<uint32_t*>(blk.p + o_pins + 2 * up64(N * 4));
-	uint32_t* const h_zs = reinterpret_cast<uint32_t*>(blk.p + o_pins + 3 * up64(N * 4));
-	uint32_t* const h_ze = reinterpret_cast<uint32_t*>(blk.p + o_pins + 4 * up64(N * 4));
-	pc.view_comp_pin = h_comp_pin; pc.view_pin_x = h_x; pc.view_pin_y = h_y; pc.view_pin_zs = h_zs; pc.view_pin_ze = h_ze;
-	pc.view_components = N;
-	pc.view_comp_label = reinterpret_cast<const uint64_t*>(blk.p + o_label);
-	pc.view_pin_ids_off = reinterpret_cast<const uint64_t*>(blk.p + o_off);
-	pc.view_pin_ids = reinterpret_cast<const uint32_t*>(blk.p + o_ids);
-	HT_MARK("p:enqueue");
-	const uint64_t* chosen = reinterpret_cast<const uint64_t*>(blk.p + o_choice);
-	const uint32_t* ze_plus1 = reinterpret_cast<const uint32_t*>(blk.p + o_ze);
-	const uint64_t usx = static_cast<uint64_t>(sx), usz = static_cast<uint64_t>(sz);
-	// the copies travel while the cover builds its table of the labels; it calls back when it needs the arrays
-	auto arrays_ready = [&]() {
-	CKL_HIP(hipStreamSynchronize(s));
-	host_parallel_for(N, 65536, [&](size_t lo, size_t hi) {
-		for (size_t c = lo; c < hi; c++) {
-			if (chosen[c] == kPinNoKey) { h_comp_pin[c] = kPinNone; h_x[c] = h_y[c] = h_zs[c] = h_ze[c] = 0; continue; }
-			if (ze_plus1[c] == 0) throw Error(CKL_ERR_RUNTIME, "crackle_amd: a chosen pin lies in no rank's rows");
-			h_comp_pin[c] = static_cast<uint32_t>(c);
-			const uint64_t col = chosen[c] / usz;
-			h_zs[c] = static_cast<uint32_t>(chosen[c] % usz);
-			h_ze[c] = ze_plus1[c] - 1u;
-			h_x[c] = static_cast<uint32_t>(col % usx);
-			h_y[c] = static_cast<uint32_t>(col / usx);
-		}
-	});
-	};
-	Header h;
-	h.sx = static_cast<uint32_t>(sx); h.sy = static_cast<uint32_t>(sy); h.sz = static_cast<uint32_t>(sz);
-	return pins_cover_host(pc, sx, sy, sz, nc, N, h.pin_index_width(), stored_width, auto_bgcolor, manual_bgcolor, arrays_ready, table);
-}
-
-// The whole pin stage of a volume that one device holds: the passes of pin_candidates_device, then the chosen
-// runs' ends, lengths, offsets (a device scan) and ids without a visit to the host, then pins_section_from_device.
-// Volumes whose id lists pass the budget (long z-runs chosen by many components) take pin_candidates_device's
-// route, which reduces the chosen runs to the distinct ones first.
-template <typename LABEL>
-std::vector<uint8_t> pins_section_plain(
-	ckl_encoder& e, const LABEL* labels, const uint32_t* cc, const uint64_t* comp_label, int64_t sx, int64_t sy, int64_t sz, uint64_t N,
-	const std::vector<uint32_t>& nc, int index_width, int stored_width, bool auto_bgcolor, int64_t manual_bgcolor
-) {
-	hipStream_t s = e.stream2;
-	if (N >= kPinNone) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many pins");
-	unsigned long long* choice = nullptr;
-	const uint64_t* first_any = nullptr;
-	PinVolume v;
-	// The labels' first runs are final after the first column pass: their lists are made there and come to the host
-	// on a stream of their own, and the host builds the label table (7 ms at C4) while the later passes still run.
-	PinLabelLists lists;
-	pin_passes_device<LABEL>(e, labels, cc, sx, sy, sz, N, v, choice, first_any,
-		[&](const uint64_t* fa) { pin_label_table_enqueue(e, comp_label, fa, N, lists); });
-	const uint32_t nb = static_cast<uint32_t>((N + kPinBlock - 1) / kPinBlock);
-	const uint32_t pieces = static_cast<uint32_t>((N + kPinScanPiece - 1) / kPinScanPiece);
-	DevBuf<uint32_t> d_zep, d_count, d_ze, d_ids;
-	DevBuf<unsigned long long> d_piece, d_off;
-	d_zep.ensure(N); d_count.ensure(N); d_piece.ensure(static_cast<size_t>(pieces) + 1); d_off.ensure(N + 1);
-	CKL_HIP(hipMemsetAsync(d_zep.p, 0, N * sizeof(uint32_t), s));
-	hipLaunchKernelGGL((k_pin_extent<LABEL, false, true>), dim3(nb), dim3(kPinBlock), 0, s, labels, v, choice, static_cast<uint32_t>(N), d_zep.p);
-	hipLaunchKernelGGL(k_pin_id_counts, dim3(nb), dim3(kPinBlock), 0, s, choice, d_zep.p, v.sz, N, d_count.p);
-	hipLaunchKernelGGL(k_pin_scan_pieces, dim3(pieces), dim3(kPinBlock), 0, s, d_count.p, N, d_piece.p);
-	hipLaunchKernelGGL(k_pin_scan_tops, dim3(1), dim3(kPinBlock), 0, s, d_piece.p, pieces);
-	hipLaunchKernelGGL(k_pin_scan_offsets, dim3(pieces), dim3(kPinBlock), 0, s, d_count.p, N, d_piece.p, pieces, d_off.p);
-	std::shared_ptr<const PinLabelTable> table;
-	{
-		PinCandidates lc;
-		pin_label_table_collect(e, lists, lc);
-		HT_MARK("p:lists");
-		table = pins_label_table_host(lc.label_value, lc.label_first);
-		HT_MARK("p:table");
-	}
-	const uint64_t total = download(d_off.p + N, 1, s)[0];
-	HT_MARK("p:passes");
-	uint64_t id_budget = 1ull << 26;      // 256 MiB of ids
-	if (const char* env = getenv("CKL_PIN_IDS_BUDGET")) id_budget = static_cast<uint64_t>(std::max(0, atoi(env)));      // testing: forces the distinct-pin path
-	if (total > id_budget || getenv("CKL_PINS_HOST_BOOKKEEPING")) {
-		const PinCandidates pc = pin_candidates_device<LABEL>(e, labels, cc, comp_label, sx, sy, sz, N, &v, choice, first_any);
-		HT_MARK("pins_device");
-		return pins_cover_host(pc, sx, sy, sz, nc, N, index_width, stored_width, auto_bgcolor, manual_bgcolor);
-	}
-	d_ze.ensure(N); d_ids.ensure(total + 1);
-	hipLaunchKernelGGL(k_pin_minus1, dim3(nb), dim3(kPinBlock), 0, s, d_zep.p, N, d_ze.p);
-	hipLaunchKernelGGL(k_pin_ids, dim3(nb), dim3(kPinBlock), 0, s, v, choice, d_ze.p, reinterpret_cast<const uint64_t*>(d_off.p), static_cast<uint32_t>(N), d_ids.p);
-	std::vector<uint8_t> bin = pins_section_from_device(e, sx, sy, sz, N, nc, comp_label, first_any, reinterpret_cast<const uint64_t*>(choice), d_zep.p,
-		reinterpret_cast<const uint64_t*>(d_off.p), d_ids.p, stored_width, auto_bgcolor, manual_bgcolor, table.get());
-	HT_MARK("pins_host");
-	return bin;
 }
 
 // The flat label section (labels.hpp:92-152) on device: sort + unique of the component
@@ -2428,6 +1881,38 @@ uint64_t flat_section(ckl_encoder& e, uint64_t N, int stored_width, int componen
 	return 8 + static_cast<uint64_t>(nu) * stored_width + static_cast<uint64_t>(ns) * component_width + N * static_cast<uint64_t>(byte_width(nu));
 }
 
+// The stream's header as the volume's statistics decide it (crackle.hpp:50-64, 233-235) unless the overrides do;
+// of an empty volume (all statistics 0) it is the whole stream (crackle.hpp:96-98).  num_label_bytes comes later.
+Header stream_header(int data_width, int64_t sx, int64_t sy, int64_t sz, const VolumeStats& st, bool allow_pins, bool fortran_order, uint64_t markov_model_order, const ckl_encode_overrides* ov) {
+	Header head;
+	head.crack_format = IMPERMISSIBLE;
+	head.label_format = PINS_VARIABLE_WIDTH;
+	if (static_cast<int64_t>(st.pairs) < static_cast<int64_t>(static_cast<uint64_t>(sx) * sy * sz) / 2) {   // crackle.hpp:50-55
+		head.crack_format = PERMISSIBLE;
+		head.label_format = FLAT;
+	}
+	if (ov && ov->force_crack_format >= 0) {
+		head.crack_format = ov->force_crack_format;
+		head.label_format = ov->force_crack_format == PERMISSIBLE ? FLAT : PINS_VARIABLE_WIDTH;
+	}
+	if (sz == 1 || !allow_pins) head.label_format = FLAT;           // crackle.hpp:62-64
+	if (ov && ov->force_label_format >= 0) head.label_format = ov->force_label_format;
+	head.is_signed = false;
+	head.data_width = data_width;
+	head.stored_data_width = ov && ov->force_stored_width ? ov->force_stored_width : byte_width(st.max_label);      // crackle.hpp:233-235
+	head.sx = static_cast<uint32_t>(sx); head.sy = static_cast<uint32_t>(sy); head.sz = static_cast<uint32_t>(sz);
+	head.log2_grid_size = 31;
+	head.fortran_order = fortran_order;
+	head.markov_model_order = static_cast<int>(markov_model_order & 0xFF);
+	head.is_sorted = true;
+	return head;
+}
+inline std::vector<uint8_t> header_bytes(const Header& head) {
+	std::vector<uint8_t> hb;
+	head.write(hb);
+	return hb;
+}
+
 template <typename LABEL>
 void encode_typed(
 	ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz,
@@ -2443,61 +1928,27 @@ void encode_typed(
 	g_ht = &ht;
 	VolumeStats st;
 	e.trail_zeroed = false;
-	const bool planes_cached = ov && voxels > 0 && e.planes_for == static_cast<const void*>(labels)
-		&& e.planes_dims[0] == sx && e.planes_dims[1] == sy && e.planes_dims[2] == sz;
+	const bool have_planes = ov && voxels > 0 && planes_cached(e, labels, sx, sy, sz);
 	e.planes_for = nullptr;       // single use: the caller may change the volume afterwards
 	const bool labels_first = getenv("CKL_NO_OVERLAP") || static_cast<uint64_t>(sx) * sy > (1536ull * 1536ull)
 		|| (getenv("CKL_LABELS_AT_WALK") && atoi(getenv("CKL_LABELS_AT_WALK")) == 0);
 	// (a label stream that starts in front of the graph kernel sizes its run arrays from the planes' counts: no deferral then)
-	if (voxels > 0 && !planes_cached) planes_pass<LABEL>(e, labels, sx, sy, sz, &st, !labels_first);
-	else if (planes_cached) st = e.planes_stats;      // overrides that force nothing still decide from the volume
+	if (voxels > 0 && !have_planes) planes_pass<LABEL>(e, labels, sx, sy, sz, &st, !labels_first);
+	else if (have_planes) st = e.planes_stats;      // overrides that force nothing still decide from the volume
 	ht.mark("planes");
 	bool graph_done = false;
 	if (e.planes_deferred) {
 		// the planes kernel's counts are still on the device: the graph kernel goes behind it without a round
 		// trip (it reads the crack format's deciding pair count there), both kernels' counts come in one
-		int perm_mode = 2;
-		if (ov && ov->force_crack_format >= 0) perm_mode = ov->force_crack_format == PERMISSIBLE ? 1 : 0;
 		e.trail_for = nullptr;
-		graph_pass(e, sx, sy, sz, perm_mode, &st);
+		graph_pass(e, sx, sy, sz, ov && ov->force_crack_format >= 0 ? graph_format(ov->force_crack_format == PERMISSIBLE) : GraphFormat::ON_DEVICE, &st);
 		graph_done = true;
 		ht.mark("graph");
 	}
-	int stored_width = byte_width(st.max_label);                     // crackle.hpp:233-235
-	if (ov && ov->force_stored_width) stored_width = ov->force_stored_width;
-
-	Header head;
-	head.crack_format = IMPERMISSIBLE;
-	head.label_format = PINS_VARIABLE_WIDTH;
-	if (static_cast<int64_t>(st.pairs) < static_cast<int64_t>(voxels) / 2) {   // crackle.hpp:50-55
-		head.crack_format = PERMISSIBLE;
-		head.label_format = FLAT;
-	}
-	if (ov && ov->force_crack_format >= 0) {
-		head.crack_format = ov->force_crack_format;
-		head.label_format = ov->force_crack_format == PERMISSIBLE ? FLAT : PINS_VARIABLE_WIDTH;
-	}
-	if (sz == 1 || !allow_pins) head.label_format = FLAT;           // crackle.hpp:62-64
-	if (ov && ov->force_label_format >= 0) head.label_format = ov->force_label_format;
+	Header head = stream_header(static_cast<int>(sizeof(LABEL)), sx, sy, sz, st, allow_pins, fortran_order, markov_model_order, ov);
+	const int stored_width = head.stored_data_width;
 	e.uploads_by_kernel = head.label_format == FLAT;
-	head.is_signed = false;
-	head.data_width = static_cast<int>(sizeof(LABEL));
-	head.stored_data_width = stored_width;
-	head.sx = static_cast<uint32_t>(sx); head.sy = static_cast<uint32_t>(sy); head.sz = static_cast<uint32_t>(sz);
-	head.log2_grid_size = 31;
-	head.fortran_order = fortran_order;
-	head.markov_model_order = static_cast<int>(markov_model_order & 0xFF);
-	head.is_sorted = true;
-
-	if (voxels == 0) {   // crackle.hpp:96-98
-		std::vector<uint8_t> hb;
-		head.write(hb);
-		uint8_t* o = static_cast<uint8_t*>(malloc(hb.size()));
-		if (!o) throw Error(CKL_ERR_RUNTIME, "crackle_amd: out of host memory");
-		memcpy(o, hb.data(), hb.size());
-		*out = o; *out_len = hb.size();
-		return;
-	}
+	if (voxels == 0) { hand_out(header_bytes(head), OutAlloc::MALLOC, out, out_len); return; }
 	if (optimize_pins) throw Error(CKL_ERR_ARG, "crackle_amd: allow_pins=2 (find_optimal_pins) is out of scope");
 	if (head.label_format != FLAT && head.label_format != PINS_VARIABLE_WIDTH) throw Error(CKL_ERR_ARG, "crackle_amd: unsupported label format");
 	if (head.markov_model_order > 13) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order > 13 is not supported on device");
@@ -2513,11 +1964,11 @@ void encode_typed(
 	// labels: 0.5 ms on the host.  It fits since the slab's labels are exchanged unsorted.)
 	bool labels_at_walk = false;
 	if (labels_first && !graph_done) flat_enqueue(e, sx, sy, sz);
-	const bool trail_cached = !graph_done && planes_cached && ov && ov->has_model && head.markov_model_order > 0 && e.trail_for == static_cast<const void*>(labels)
+	const bool trail_cached = !graph_done && have_planes && ov && ov->has_model && head.markov_model_order > 0 && e.trail_for == static_cast<const void*>(labels)
 		&& e.trail_perm == (head.crack_format == PERMISSIBLE) && e.trail_order == head.markov_model_order;
 	e.trail_for = nullptr;
 	if (graph_done && e.graph_permissible != (head.crack_format == PERMISSIBLE)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: device and host disagree on the crack format");
-	if (!trail_cached && !graph_done) graph_pass(e, sx, sy, sz, head.crack_format == PERMISSIBLE ? 1 : 0);
+	if (!trail_cached && !graph_done) graph_pass(e, sx, sy, sz, graph_format(head.crack_format == PERMISSIBLE));
 	ht.mark("graph");
 	if (!labels_first) {
 		uint32_t max_special = 0;
@@ -2531,20 +1982,19 @@ void encode_typed(
 	const bool permissible = head.crack_format == PERMISSIBLE;
 	// if no slice has a crack edge the reference resets the markov order to 0 (crackle.hpp:107-118)
 	{
-		const uint64_t interior = static_cast<uint64_t>(sx > 0 ? sx - 1 : 0) * sy + static_cast<uint64_t>(sx) * (sy > 0 ? sy - 1 : 0);
 		bool any = false;
-		for (int64_t z = 0; z < sz && !any; z++) {
-			const uint64_t differ = static_cast<uint64_t>(e.count_v[z]) + e.count_h[z];
-			any = (permissible ? interior - differ : differ) > 0;
-		}
+		for (int64_t z = 0; z < sz && !any; z++) any = crack_edges(e, sx, sy, z, permissible) > 0;
 		if (!any && !(ov && ov->has_model)) head.markov_model_order = 0;
 	}
 	std::vector<uint8_t> forced_model;
-	const std::vector<uint8_t>* model_in = nullptr;
+	CrackRequest crq;
+	crq.permissible = permissible;
+	crq.markov_order = head.markov_model_order;
+	crq.reuse_trail = trail_cached;
 	if (ov && ov->has_model && head.markov_model_order > 0) {
 		const size_t rows = static_cast<size_t>(1) << (2 * head.markov_model_order);
 		forced_model.assign(ov->model, ov->model + rows * 4);
-		model_in = &forced_model;
+		crq.model = &forced_model;
 	}
 
 	FlatResult fr;
@@ -2556,12 +2006,9 @@ void encode_typed(
 	// costs a few more; 2 bits per code (markov: at most 3), BOC index of a few chains per slice
 	uint64_t est_code_bytes = 0;
 	{
-		const uint64_t interior = static_cast<uint64_t>(sx > 0 ? sx - 1 : 0) * sy + static_cast<uint64_t>(sx) * (sy > 0 ? sy - 1 : 0);
 		const int xw = byte_width(static_cast<uint64_t>(sx) + 1), yw = byte_width(static_cast<uint64_t>(sy) + 1);
 		for (int64_t z = 0; z < sz; z++) {
-			const uint64_t differ = static_cast<uint64_t>(e.count_v[z]) + e.count_h[z];
-			const uint64_t E = permissible ? interior - differ : differ;
-			const uint64_t codes = E + 4ull * (static_cast<uint64_t>(e.count_special[z]) + e.count_corner[z]) + 16;
+			const uint64_t codes = crack_edges(e, sx, sy, z, permissible) + 4ull * (static_cast<uint64_t>(e.count_special[z]) + e.count_corner[z]) + 16;
 			est_code_bytes += (head.markov_model_order ? (3 * codes + 7) / 8 : (codes + 3) / 4) + 8;
 			est_code_bytes += 4 + yw + 64ull * (yw + 2 * xw);
 		}
@@ -2587,7 +2034,7 @@ void encode_typed(
 			// device passes above; the order-sensitive cover runs on the host (ckl_pins.hip)
 			if (N > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
 			e.d_cc_volume.ensure(voxels);
-			launch_paint_components(s2, e.d_planes.p, e.row_words, e.plane_words, sx, sy, sz, e.d_word_base.p, e.d_rbase.p, e.d_run_cc.p, e.d_comp_off.p, 0u, e.d_cc_volume.p);
+			launch_paint_components(s2, plane_v(e), e.row_words, e.plane_words, sx, sy, sz, e.d_word_base.p, e.d_rbase.p, e.d_run_cc.p, e.d_comp_off.p, 0u, e.d_cc_volume.p);
 			pins_binary = pins_section_plain<LABEL>(e, labels, e.d_cc_volume.p, e.d_mapping.p, sx, sy, sz, N, fr.ncomp, head.pin_index_width(), stored_width, auto_bgcolor, manual_bgcolor);
 			label_bytes = pins_binary.size();
 		}
@@ -2622,15 +2069,13 @@ void encode_typed(
 		}
 	};
 
-	CrackResult cr;
-	std::vector<uint8_t> model, stored_model;
-	if (getenv("CKL_NO_OVERLAP")) {   // diagnostic: kernel timings without the two streams competing
-		crack_pass(e, sx, sy, sz, permissible, head.markov_model_order, false, model_in, nullptr, &model, &cr, std::function<void()>(), trail_cached);
-		label_side();
-	}
-	else crack_pass(e, sx, sy, sz, permissible, head.markov_model_order, false, model_in, nullptr, &model, &cr, label_side, trail_cached);
+	const bool no_overlap = getenv("CKL_NO_OVERLAP") != nullptr;      // diagnostic: kernel timings without the two streams competing
+	if (!no_overlap) crq.overlap = label_side;
+	const CrackResult cr = crack_pass(e, sx, sy, sz, crq);
+	if (no_overlap) label_side();
 	ht.mark("cracks");
-	if (head.markov_model_order > 0) stored_model = markov_model_to_stored(model);
+	std::vector<uint8_t> stored_model;
+	if (head.markov_model_order > 0) stored_model = markov_model_to_stored(cr.model);
 
 	// assembly (crackle.hpp:171-216), straight into the caller's buffer:
 	// header | z-index + crc | labels | model | crack codes | labels crc | slice crcs
@@ -2707,12 +2152,11 @@ void encode_typed(
 		ht.mark("codes_d2h");
 		CKL_HIP(hipGetLastError());
 		CKL_HIP(hipEventElapsedTime(&e.pipeline_ms, e.ev0, e.ev1));
-		CKL_HIP(hipEventElapsedTime(&e.trail_ms, e.evk0, e.evk1));
 		CKL_HIP(hipEventElapsedTime(&e.dominant_ms, e.evd0, e.evd1));      // the encoder's longest kernel: k_trail_walk
 	}
 	catch (...) {
 		// the codes' background copy may already be queued into `o`: it must be over before the block goes back to the cache
-		if (e.host_copy_pending) { (void)hipStreamSynchronize(e.stream_copy); e.host_copy_pending = false; }
+		drain_host_copy(e, true);
 		host_out_free(o);
 		throw;
 	}
@@ -2730,12 +2174,7 @@ void reencode_markov(const uint8_t* buf, uint64_t n, int markov_order, int devic
 	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
 	Header head = Header::parse(buf, n);
 	if (markov_order < 0 || markov_order > 13) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [0, 13] on device");
-	auto copy_out = [&](const uint8_t* p, uint64_t len) {
-		uint8_t* o = static_cast<uint8_t*>(host_out_alloc(len));
-		memcpy(o, p, len);
-		*out = o; *out_len = len;
-	};
-	if (head.markov_model_order == markov_order) { copy_out(buf, n); return; }      // crackle.hpp:887-889
+	if (head.markov_model_order == markov_order) { hand_out(buf, n, OutAlloc::HOST_OUT, out, out_len); return; }      // crackle.hpp:887-889
 	// Version 0 streams (24-byte header, no crcs) stay version 0, as src/crackle.hpp:947-984 means them to: the
 	// reference's own output for them is broken — its header vector has 29 bytes of which 24 are written
 	// (src/header.hpp:277-281), so five stray zero bytes follow the header (tests/golden/v0.npz keeps a sample) —
@@ -2764,7 +2203,7 @@ void reencode_markov(const uint8_t* buf, uint64_t n, int markov_order, int devic
 	if (ckl_decoder_create(buf, n, 0, -1, device, &dec.d) != CKL_OK) throw Error(CKL_ERR_RUNTIME, ckl_last_error());
 	lap("decoder_create");
 	CrackResult cr;
-	std::vector<uint8_t> model, stored_model;
+	std::vector<uint8_t> stored_model;
 	head.markov_model_order = markov_order;
 	if (head.voxels() > 0) {
 		const uint32_t *cv = nullptr, *ch = nullptr;
@@ -2785,16 +2224,19 @@ void reencode_markov(const uint8_t* buf, uint64_t n, int markov_order, int devic
 		CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, 2 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
 		hipLaunchKernelGGL(k_planes_from_cracks, dim3(static_cast<uint32_t>((plane_words + kBlock - 1) / kBlock), ns), dim3(kBlock), 0, s,
 			cv, ch, head.sx, head.sy, row_words, plane_words, permissible ? 1u : 0u,
-			e.d_planes.p, e.d_planes.p + plane_words * ns, e.d_count_vh.p, ns);
+			plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
 		std::vector<uint32_t> c = download(e.d_count_vh.p, 2 * static_cast<size_t>(ns), s);
 		e.count_v.assign(c.begin(), c.begin() + ns);
 		e.count_h.assign(c.begin() + ns, c.end());
 		lap("planes");
-		graph_pass(e, head.sx, head.sy, head.sz, permissible);
+		graph_pass(e, head.sx, head.sy, head.sz, graph_format(permissible));
 		lap("graph");
-		crack_pass(e, head.sx, head.sy, head.sz, permissible, markov_order, false, nullptr, nullptr, &model, &cr);
+		CrackRequest crq;
+		crq.permissible = permissible;
+		crq.markov_order = markov_order;
+		cr = crack_pass(e, head.sx, head.sy, head.sz, crq);
 		lap("cracks");
-		if (markov_order > 0) stored_model = markov_model_to_stored(model);
+		if (markov_order > 0) stored_model = markov_model_to_stored(cr.model);
 	}
 	else cr.code_len.assign(sz, 0);
 
@@ -2844,7 +2286,7 @@ int ckl_encoder_create(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int 
 		select_device(device);
 		std::unique_ptr<ckl_encoder> e(new ckl_encoder());
 		e->device = device;
-		e->max_sx = sx; e->max_sy = sy; e->max_sz = sz; e->dtype_bytes = dtype_bytes;
+		e->dtype_bytes = dtype_bytes;
 		CKL_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
 		{
 			// the label stream ahead of the trail stream: its many small kernels should be through before
@@ -2855,8 +2297,6 @@ int ckl_encoder_create(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int 
 		}
 		CKL_HIP(hipEventCreate(&e->ev0));
 		CKL_HIP(hipEventCreate(&e->ev1));
-		CKL_HIP(hipEventCreate(&e->evk0));
-		CKL_HIP(hipEventCreate(&e->evk1));
 		CKL_HIP(hipEventCreate(&e->evd0));
 		CKL_HIP(hipEventCreate(&e->evd1));
 		CKL_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
@@ -2875,21 +2315,13 @@ int ckl_encoder_run(
 		if (!e || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		check_dims(sx, sy, sz, e->dtype_bytes, 0);
 		if (markov_model_order > 15) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [0, 15]");
-		select_device(e->device);
-		if (e->host_copy_pending) {      // the previous run's codes are still on their way out of d_codes_out
-			CKL_HIP(hipStreamSynchronize(e->stream_copy));
-			e->host_copy_pending = false;
-		}
-		wait_for_default_stream(e->stream, e->ev_in);
-		wait_for_default_stream(e->stream2, e->ev_in);
+		enter(e);
+		drain_host_copy(*e);      // the previous run's codes are still on their way out of d_codes_out
 		const auto t_run0 = std::chrono::steady_clock::now();
-#define CKL_ENC(T) encode_typed<T>(*e, reinterpret_cast<const T*>(labels_device), sx, sy, sz, allow_pins != 0, fortran_order != 0, \
-	markov_model_order, optimize_pins != 0, auto_bgcolor != 0, manual_bgcolor, overrides, out, out_len)
-		if (e->dtype_bytes == 1) CKL_ENC(uint8_t);
-		else if (e->dtype_bytes == 2) CKL_ENC(uint16_t);
-		else if (e->dtype_bytes == 4) CKL_ENC(uint32_t);
-		else CKL_ENC(uint64_t);
-#undef CKL_ENC
+		with_label_type(e->dtype_bytes, [&](auto t) {
+			encode_typed(*e, static_cast<const typename decltype(t)::type*>(labels_device), sx, sy, sz, allow_pins != 0, fortran_order != 0,
+				markov_model_order, optimize_pins != 0, auto_bgcolor != 0, manual_bgcolor, overrides, out, out_len);
+		});
 		if (getenv("CKL_PROFILE")) {
 			fprintf(stderr, "[ckl encoder_run ms] encode=%.2f\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run0).count());
 		}
@@ -2919,11 +2351,8 @@ int ckl_encoder_async_host_copy(ckl_encoder* e, int on) {
 int ckl_encoder_host_wait(ckl_encoder* e) {
 	return guard([&] {
 		if (!e) throw Error(CKL_ERR_ARG, "crackle_amd: null encoder");
-		if (e->host_copy_pending) {
-			select_device(e->device);
-			CKL_HIP(hipStreamSynchronize(e->stream_copy));
-			e->host_copy_pending = false;
-		}
+		if (e->host_copy_pending) select_device(e->device);
+		drain_host_copy(*e);
 	});
 }
 
@@ -2965,11 +2394,8 @@ int ckl_encoder_stats(
 	uint64_t* max_label, uint64_t* pixel_pairs, uint64_t* first_voxel, uint64_t* last_voxel
 ) {
 	return guard([&] {
-		if (!e) throw Error(CKL_ERR_ARG, "crackle_amd: null encoder");
+		enter(e);
 		check_dims(sx, sy, sz, e->dtype_bytes, 0);
-		select_device(e->device);
-		wait_for_default_stream(e->stream, e->ev_in);
-		wait_for_default_stream(e->stream2, e->ev_in);
 		const uint64_t voxels = static_cast<uint64_t>(sx) * sy * sz;
 		VolumeStats st;
 		e->planes_for = nullptr;
@@ -2984,10 +2410,7 @@ int ckl_encoder_stats(
 			struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{ e->stream };
 			CKL_HIP(hipMemcpyAsync(&f, base, e->dtype_bytes, hipMemcpyDeviceToHost, e->stream));
 			CKL_HIP(hipMemcpyAsync(&l, base + (voxels - 1) * e->dtype_bytes, e->dtype_bytes, hipMemcpyDeviceToHost, e->stream));
-			if (e->dtype_bytes == 1) planes_pass<uint8_t>(*e, reinterpret_cast<const uint8_t*>(labels_device), sx, sy, sz, &st);
-			else if (e->dtype_bytes == 2) planes_pass<uint16_t>(*e, reinterpret_cast<const uint16_t*>(labels_device), sx, sy, sz, &st);
-			else if (e->dtype_bytes == 4) planes_pass<uint32_t>(*e, reinterpret_cast<const uint32_t*>(labels_device), sx, sy, sz, &st);
-			else planes_pass<uint64_t>(*e, reinterpret_cast<const uint64_t*>(labels_device), sx, sy, sz, &st);
+			planes_pass_any(*e, labels_device, sx, sy, sz, &st);
 			CKL_HIP(hipStreamSynchronize(e->stream));      // (planes_pass has waited for the stream already: this returns at once)
 			st.first = f; st.last = l;
 			e->planes_for = labels_device;
@@ -3009,24 +2432,20 @@ int ckl_encoder_markov_stats(
 		if (!e || !hist) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		check_dims(sx, sy, sz, e->dtype_bytes, 0);
 		if (markov_model_order == 0 || markov_model_order > 13) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [1, 13]");
-		select_device(e->device);
-		wait_for_default_stream(e->stream, e->ev_in);
-		wait_for_default_stream(e->stream2, e->ev_in);
+		enter(e);
 		const size_t rows = static_cast<size_t>(1) << (2 * markov_model_order);
 		std::vector<uint32_t> h(rows * 4, 0);
 		if (static_cast<uint64_t>(sx) * sy * sz > 0) {
-			const bool perm = crack_format == PERMISSIBLE;
-			const int order = static_cast<int>(markov_model_order);
-			const bool cached = e->planes_for == labels_device && e->planes_dims[0] == sx && e->planes_dims[1] == sy && e->planes_dims[2] == sz;
-			if (cached) {}
-			else if (e->dtype_bytes == 1) planes_pass<uint8_t>(*e, reinterpret_cast<const uint8_t*>(labels_device), sx, sy, sz, nullptr);
-			else if (e->dtype_bytes == 2) planes_pass<uint16_t>(*e, reinterpret_cast<const uint16_t*>(labels_device), sx, sy, sz, nullptr);
-			else if (e->dtype_bytes == 4) planes_pass<uint32_t>(*e, reinterpret_cast<const uint32_t*>(labels_device), sx, sy, sz, nullptr);
-			else planes_pass<uint64_t>(*e, reinterpret_cast<const uint64_t*>(labels_device), sx, sy, sz, nullptr);
+			CrackRequest crq;
+			crq.goal = CrackGoal::HISTOGRAM;
+			crq.permissible = crack_format == PERMISSIBLE;
+			crq.markov_order = static_cast<int>(markov_model_order);
+			const bool cached = planes_cached(*e, labels_device, sx, sy, sz);
+			if (!cached) planes_pass_any(*e, labels_device, sx, sy, sz, nullptr);
 			e->trail_for = nullptr;
-			graph_pass(*e, sx, sy, sz, perm);
-			crack_pass(*e, sx, sy, sz, perm, order, true, nullptr, &h, nullptr, nullptr);
-			if (cached) { e->trail_for = labels_device; e->trail_perm = perm; e->trail_order = order; }      // (only beside cached planes: the run checks both)
+			graph_pass(*e, sx, sy, sz, graph_format(crq.permissible));
+			h = crack_pass(*e, sx, sy, sz, crq).hist;
+			if (cached) { e->trail_for = labels_device; e->trail_perm = crq.permissible; e->trail_order = crq.markov_order; }      // (only beside cached planes: the run checks both)
 		}
 		memcpy(hist, h.data(), h.size() * sizeof(uint32_t));
 	});
@@ -3036,27 +2455,17 @@ int ckl_encoder_markov_stats(
 // painted into cc_device (null: the session's own volume); returns where they are
 static uint32_t* encoder_components(ckl_encoder* e, const void* labels_device, int64_t sx, int64_t sy, int64_t sz, uint32_t id_base, uint32_t* cc_device, uint32_t* ncomp_host) {
 	check_dims(sx, sy, sz, e->dtype_bytes, 0);
-	select_device(e->device);
-	wait_for_default_stream(e->stream, e->ev_in);
-	wait_for_default_stream(e->stream2, e->ev_in);
+	enter(e);
 	const uint64_t voxels = static_cast<uint64_t>(sx) * sy * sz;
 	if (voxels == 0) return cc_device;
-	const bool cached = e->planes_for == labels_device && e->planes_dims[0] == sx && e->planes_dims[1] == sy && e->planes_dims[2] == sz;
 	FlatResult fr;
-#define CKL_COMP(T) do { \
-		if (!cached) planes_pass<T>(*e, reinterpret_cast<const T*>(labels_device), sx, sy, sz, nullptr); \
-		flat_enqueue(*e, sx, sy, sz); \
-		flat_collect<T>(*e, reinterpret_cast<const T*>(labels_device), sx, sy, sz, fr); \
-	} while (0)
-	if (e->dtype_bytes == 1) CKL_COMP(uint8_t);
-	else if (e->dtype_bytes == 2) CKL_COMP(uint16_t);
-	else if (e->dtype_bytes == 4) CKL_COMP(uint32_t);
-	else CKL_COMP(uint64_t);
-#undef CKL_COMP
+	if (!planes_cached(*e, labels_device, sx, sy, sz)) planes_pass_any(*e, labels_device, sx, sy, sz, nullptr);
+	flat_enqueue(*e, sx, sy, sz);
+	with_label_type(e->dtype_bytes, [&](auto t) { flat_collect(*e, static_cast<const typename decltype(t)::type*>(labels_device), sx, sy, sz, fr); });
 	if (fr.total + id_base > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
 	hipStream_t s2 = e->stream2;
 	if (!cc_device) { e->d_cc_volume.ensure(voxels); cc_device = e->d_cc_volume.p; }
-	launch_paint_components(s2, e->d_planes.p, e->row_words, e->plane_words, sx, sy, sz, e->d_word_base.p, e->d_rbase.p, e->d_run_cc.p, e->d_comp_off.p, id_base, cc_device);
+	launch_paint_components(s2, plane_v(*e), e->row_words, e->plane_words, sx, sy, sz, e->d_word_base.p, e->d_rbase.p, e->d_run_cc.p, e->d_comp_off.p, id_base, cc_device);
 	for (int64_t z = 0; z < sz; z++) ncomp_host[z] = fr.ncomp[z];
 	return cc_device;
 }
@@ -3085,146 +2494,6 @@ int ckl_encoder_components_device(
 	});
 }
 
-int ckl_encoder_pin_labels(
-	ckl_encoder* e, const void* labels_device, const uint32_t* cc_device,
-	int64_t sx, int64_t sy, int64_t sz, const uint32_t* ncomp_host,
-	int stored_width, int auto_bgcolor, int64_t manual_bgcolor,
-	uint8_t** out, uint64_t* out_len
-) {
-	return guard([&] {
-		if (!e || !labels_device || !cc_device || !ncomp_host || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		if (sx <= 0 || sy <= 0 || sz <= 0) throw Error(CKL_ERR_ARG, "crackle_amd: empty volume");
-		if (sx > 0xFFFFFFFFll || sy > 0xFFFFFFFFll || sz > 0xFFFFFFFFll) throw Error(CKL_ERR_ARG, "crackle_amd: dimensions must fit 32 bits");
-		if (stored_width != 1 && stored_width != 2 && stored_width != 4 && stored_width != 8) throw Error(CKL_ERR_ARG, "crackle_amd: stored width must be 1, 2, 4 or 8 bytes");
-		select_device(e->device);
-		wait_for_default_stream(e->stream2, e->ev_in);
-		std::vector<uint32_t> nc(ncomp_host, ncomp_host + sz);
-		uint64_t N = 0;
-		for (uint32_t c : nc) N += c;
-		if (N == 0 || N > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: component counts out of range");
-		Header h;
-		h.sx = static_cast<uint32_t>(sx); h.sy = static_cast<uint32_t>(sy); h.sz = static_cast<uint32_t>(sz);
-		hipStream_t s = e->stream2;
-		const uint64_t voxels = static_cast<uint64_t>(sx) * sy * sz;
-		// label of every component, read where the id changes along x (every component has such a voxel)
-		e->d_mapping.ensure(N + 1);
-		e->d_slice_err2.ensure(1);
-		CKL_HIP(hipMemsetAsync(e->d_mapping.p, 0, N * sizeof(uint64_t), s));
-		CKL_HIP(hipMemsetAsync(e->d_slice_err2.p, 0, sizeof(uint32_t), s));
-		std::vector<uint8_t> bin;
-		const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((voxels + kPinBlock - 1) / kPinBlock, 0x7FFFFFFFull));
-#define CKL_PINS(T) do { \
-			hipLaunchKernelGGL(k_pin_component_labels<T>, dim3(blocks), dim3(kPinBlock), 0, s, reinterpret_cast<const T*>(labels_device), cc_device, voxels, static_cast<uint32_t>(sx), N, \
-				reinterpret_cast<unsigned long long*>(e->d_mapping.p), e->d_slice_err2.p); \
-			if (download(e->d_slice_err2.p, 1, s)[0]) throw Error(CKL_ERR_ARG, "crackle_amd: component id out of range"); \
-			bin = pins_section_plain<T>(*e, reinterpret_cast<const T*>(labels_device), cc_device, e->d_mapping.p, sx, sy, sz, N, nc, h.pin_index_width(), stored_width, auto_bgcolor != 0, manual_bgcolor); \
-		} while (0)
-		if (e->dtype_bytes == 1) CKL_PINS(uint8_t);
-		else if (e->dtype_bytes == 2) CKL_PINS(uint16_t);
-		else if (e->dtype_bytes == 4) CKL_PINS(uint32_t);
-		else CKL_PINS(uint64_t);
-#undef CKL_PINS
-		uint8_t* p = static_cast<uint8_t*>(host_out_alloc(bin.size() ? bin.size() : 1));
-		memcpy(p, bin.data(), bin.size());
-		*out = p;
-		*out_len = bin.size();
-	});
-}
-
-
-#define CKL_ROWS_DISPATCH(CALL) do { \
-		if (e->dtype_bytes == 1) { typedef uint8_t T; CALL; } \
-		else if (e->dtype_bytes == 2) { typedef uint16_t T; CALL; } \
-		else if (e->dtype_bytes == 4) { typedef uint32_t T; CALL; } \
-		else { typedef uint64_t T; CALL; } \
-	} while (0)
-
-static void pins_rows_check(const ckl_encoder* e, const void* labels, const uint32_t* cc, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t N) {
-	if (!e || !labels || !cc) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-	if (sx <= 0 || rows <= 0 || sz <= 0 || y0 < 0) throw Error(CKL_ERR_ARG, "crackle_amd: empty row slab");
-	if (sx > 0x7FFFFFF0ll || rows > 0x7FFFFFF0ll || y0 > 0x7FFFFFF0ll || sz > 65535) throw Error(CKL_ERR_ARG, "crackle_amd: row slab dimensions out of range");
-	if (N == 0 || N >= kPinNone) throw Error(CKL_ERR_ARG, "crackle_amd: component count out of range");
-	if (static_cast<unsigned __int128>(y0 + rows) * static_cast<uint64_t>(sx) * static_cast<uint64_t>(sz) >= (static_cast<unsigned __int128>(1) << 47)) throw Error(CKL_ERR_ARG, "crackle_amd: volume too large for the row-sharded pin stage");
-}
-
-int ckl_pins_rows_first(ckl_encoder* e, const void* labels_rows, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
-	uint64_t* first_any, uint64_t* first_kept, uint64_t* comp_label) {
-	return guard([&] {
-		pins_rows_check(e, labels_rows, cc_rows, sx, rows, sz, y0, n_components);
-		if (!first_any || !first_kept || !comp_label) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		select_device(e->device);
-		wait_for_default_stream(e->stream2, e->ev_in);
-		CKL_ROWS_DISPATCH(pins_rows_first<T>(*e, static_cast<const T*>(labels_rows), cc_rows, sx, rows, sz, y0, n_components, first_any, first_kept, comp_label));
-		CKL_HIP(hipStreamSynchronize(e->stream2));
-	});
-}
-
-int ckl_pins_rows_best(ckl_encoder* e, const void* labels_rows, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
-	const uint64_t* first_kept, uint64_t* best) {
-	return guard([&] {
-		pins_rows_check(e, labels_rows, cc_rows, sx, rows, sz, y0, n_components);
-		if (!first_kept || !best) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		select_device(e->device);
-		wait_for_default_stream(e->stream2, e->ev_in);
-		CKL_ROWS_DISPATCH(pins_rows_best<T>(*e, static_cast<const T*>(labels_rows), cc_rows, sx, rows, sz, y0, n_components, first_kept, best));
-	});
-}
-
-int ckl_pins_rows_extent(ckl_encoder* e, const void* labels_rows, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
-	const uint64_t* first_kept, const uint64_t* best, uint64_t* choice, uint32_t* ze_plus1) {
-	return guard([&] {
-		pins_rows_check(e, labels_rows, cc_rows, sx, rows, sz, y0, n_components);
-		if (!first_kept || !best || !choice || !ze_plus1) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		select_device(e->device);
-		wait_for_default_stream(e->stream2, e->ev_in);
-		CKL_ROWS_DISPATCH(pins_rows_extent<T>(*e, static_cast<const T*>(labels_rows), cc_rows, sx, rows, sz, y0, n_components, first_kept, best, choice, ze_plus1));
-	});
-}
-
-int ckl_pins_rows_ids(ckl_encoder* e, const uint32_t* cc_rows, int64_t sx, int64_t rows, int64_t sz, int64_t y0, uint64_t n_components,
-	const uint64_t* choice, const uint32_t* ze_plus1, const uint64_t* offsets, uint32_t* ids) {
-	return guard([&] {
-		if (!e || !cc_rows || !choice || !ze_plus1 || !offsets || !ids) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		if (sx <= 0 || rows <= 0 || sz <= 0 || y0 < 0 || n_components == 0 || n_components >= kPinNone) throw Error(CKL_ERR_ARG, "crackle_amd: row slab out of range");
-		select_device(e->device);
-		wait_for_default_stream(e->stream2, e->ev_in);
-		hipStream_t s = e->stream2;
-		PinVolume v;
-		v.sx = static_cast<uint32_t>(sx); v.sy = static_cast<uint32_t>(rows); v.sz = static_cast<uint32_t>(sz);
-		v.sxy = static_cast<uint64_t>(v.sx) * v.sy; v.key_col0 = static_cast<uint64_t>(y0) * v.sx; v.cc = cc_rows; v.mark = nullptr;
-		// k_pin_ids wants the last slice itself: the entries that are 0 ("not mine") are skipped by the row check, so ze_plus1 - 1 of the others
-		DevBuf<uint32_t> d_ze;
-		d_ze.ensure(n_components);
-		const uint32_t nb = static_cast<uint32_t>((n_components + kPinBlock - 1) / kPinBlock);
-		hipLaunchKernelGGL(k_pin_minus1, dim3(nb), dim3(kPinBlock), 0, s, ze_plus1, n_components, d_ze.p);
-		hipLaunchKernelGGL(k_pin_ids, dim3(nb), dim3(kPinBlock), 0, s, v, reinterpret_cast<const unsigned long long*>(choice), d_ze.p, offsets, static_cast<uint32_t>(n_components), ids);
-		CKL_HIP(hipStreamSynchronize(s));
-	});
-}
-
-int ckl_pins_rows_section(ckl_encoder* e, int64_t sx, int64_t sy, int64_t sz, uint64_t n_components, const uint32_t* ncomp_host,
-	const uint64_t* comp_label, const uint64_t* first_any, const uint64_t* choice, const uint32_t* ze_plus1, const uint64_t* offsets, const uint32_t* ids,
-	int stored_width, int auto_bgcolor, int64_t manual_bgcolor, uint8_t** out, uint64_t* out_len) {
-	return guard([&] {
-		if (!e || !ncomp_host || !comp_label || !first_any || !choice || !ze_plus1 || !offsets || !ids || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		if (sx <= 0 || sy <= 0 || sz <= 0) throw Error(CKL_ERR_ARG, "crackle_amd: empty volume");
-		if (stored_width != 1 && stored_width != 2 && stored_width != 4 && stored_width != 8) throw Error(CKL_ERR_ARG, "crackle_amd: stored width must be 1, 2, 4 or 8 bytes");
-		const uint64_t N = n_components;
-		if (N == 0 || N >= kPinNone) throw Error(CKL_ERR_ARG, "crackle_amd: component count out of range");
-		select_device(e->device);
-		wait_for_default_stream(e->stream2, e->ev_in);
-		std::vector<uint32_t> nc(ncomp_host, ncomp_host + sz);
-		HostTimer ht;
-		g_ht = &ht;
-		const std::vector<uint8_t> bin = pins_section_from_device(*e, sx, sy, sz, N, nc, comp_label, first_any, choice, ze_plus1, offsets, ids, stored_width, auto_bgcolor != 0, manual_bgcolor);
-		ht.mark("p:cover");
-		uint8_t* p = static_cast<uint8_t*>(host_out_alloc(bin.size() ? bin.size() : 1));
-		memcpy(p, bin.data(), bin.size());
-		*out = p;
-		*out_len = bin.size();
-	});
-}
-
 int ckl_encoder_last_timing(const ckl_encoder* e, float* pipeline_ms, float* dominant_kernel_ms) {
 	if (!e) { set_last_error("crackle_amd: null encoder"); return CKL_ERR_ARG; }
 	if (pipeline_ms) *pipeline_ms = e->pipeline_ms;
@@ -3246,28 +2515,6 @@ int ckl_encoder_walk_paths(ckl_encoder* e, uint32_t* fast_slices, uint32_t* comp
 		if (fast_slices) *fast_slices = fast;
 		if (compiled_slices) *compiled_slices = plain;
 	});
-}
-
-// grid = slices, block = kBlock: the walk's events of a slice by kind, and the longest run of events that take no decision
-// (a node with one remaining edge is left by it, a dead end returns: kEvSeg / kEvDead / kEvEnd; only kEvBseg picks an edge
-// AND leaves one behind).  counts: [slices][5] = seg, bseg, dead, end, longest run without a kEvBseg
-__global__ void __launch_bounds__(kBlock) k_trail_step_kinds(const uint32_t* __restrict__ events, const uint64_t* __restrict__ ibase, const uint32_t* __restrict__ n_events, uint32_t* __restrict__ counts) {
-	__shared__ uint32_t s_c[5];
-	const uint32_t zi = blockIdx.x;
-	if (threadIdx.x < 5) s_c[threadIdx.x] = 0u;
-	__syncthreads();
-	const uint32_t n = n_events[zi] & ~(dev::kEvFormatAddr12 | dev::kEvWalkWide);
-	const uint32_t* ev = events + ibase[zi];
-	uint32_t c[4] = { 0, 0, 0, 0 };
-	for (uint32_t i = threadIdx.x; i < n; i += kBlock) c[ev[i] >> 30]++;
-	for (int k = 0; k < 4; k++) if (c[k]) atomicAdd(&s_c[k], c[k]);
-	if (threadIdx.x == 0) {      // (one thread: a diagnostic, not a product path)
-		uint32_t run = 0, longest = 0;
-		for (uint32_t i = 0; i < n; i++) { if ((ev[i] >> 30) == 1u) run = 0; else { run++; longest = run > longest ? run : longest; } }
-		s_c[4] = longest;
-	}
-	__syncthreads();
-	if (threadIdx.x < 5) counts[zi * 5u + threadIdx.x] = s_c[threadIdx.x];
 }
 
 int ckl_encoder_walk_step_kinds(ckl_encoder* e, uint32_t* counts, uint32_t max_slices, uint32_t* n_slices) {
@@ -3300,22 +2547,8 @@ int ckl_compress(
 		check_dims(sx, sy, sz, dtype_bytes, is_signed);
 		if (!out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (static_cast<uint64_t>(sx) * sy * sz == 0) {
-			// crackle.hpp:96-98: an empty volume is just the 29-byte header; nothing to compute
-			Header head;
-			head.crack_format = IMPERMISSIBLE;              // pixel_pairs 0 < 0 / 2 is false (crackle.hpp:50-55)
-			head.label_format = (sz == 1 || !allow_pins) ? FLAT : PINS_VARIABLE_WIDTH;
-			head.data_width = dtype_bytes;
-			head.stored_data_width = 1;                     // max_label of nothing is 0
-			head.sx = static_cast<uint32_t>(sx); head.sy = static_cast<uint32_t>(sy); head.sz = static_cast<uint32_t>(sz);
-			head.fortran_order = fortran_order != 0;
-			head.markov_model_order = static_cast<int>(markov_model_order & 0xFF);
-			std::vector<uint8_t> bin;
-			head.write(bin);
-			uint8_t* p = static_cast<uint8_t*>(malloc(bin.size()));
-			if (!p) throw Error(CKL_ERR_RUNTIME, "crackle_amd: out of host memory");
-			memcpy(p, bin.data(), bin.size());
-			*out = p;
-			*out_len = bin.size();
+			// crackle.hpp:96-98: an empty volume is just the 29-byte header; nothing to compute (its statistics are all 0)
+			hand_out(header_bytes(stream_header(dtype_bytes, sx, sy, sz, VolumeStats(), allow_pins != 0, fortran_order != 0, markov_model_order, nullptr)), OutAlloc::MALLOC, out, out_len);
 			return CKL_OK;
 		}
 	}

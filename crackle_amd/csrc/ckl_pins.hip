@@ -684,11 +684,8 @@ extern "C" int ckl_pin_labels_host(
 		Header h;
 		h.sx = static_cast<uint32_t>(sx); h.sy = static_cast<uint32_t>(sy); h.sz = static_cast<uint32_t>(sz);
 		PinCandidates pc;
-		if (dtype_bytes == 1) pc = pin_candidates_host<uint8_t>(static_cast<const uint8_t*>(labels), cc, sx, sy, sz, total);
-		else if (dtype_bytes == 2) pc = pin_candidates_host<uint16_t>(static_cast<const uint16_t*>(labels), cc, sx, sy, sz, total);
-		else if (dtype_bytes == 4) pc = pin_candidates_host<uint32_t>(static_cast<const uint32_t*>(labels), cc, sx, sy, sz, total);
-		else if (dtype_bytes == 8) pc = pin_candidates_host<uint64_t>(static_cast<const uint64_t*>(labels), cc, sx, sy, sz, total);
-		else throw Error(CKL_ERR_ARG, "crackle_amd: dtype width must be 1, 2, 4 or 8 bytes");
+		if (dtype_bytes != 1 && dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8) throw Error(CKL_ERR_ARG, "crackle_amd: dtype width must be 1, 2, 4 or 8 bytes");
+		with_label_type(dtype_bytes, [&](auto t) { pc = pin_candidates_host(static_cast<const typename decltype(t)::type*>(labels), cc, sx, sy, sz, total); });
 		const std::vector<uint8_t> bin = pins_cover_host(pc, sx, sy, sz, nc, total, h.pin_index_width(), stored_width, auto_bgcolor != 0, manual_bgcolor);
 		uint8_t* p = static_cast<uint8_t*>(malloc(bin.size() ? bin.size() : 1));
 		if (!p) throw Error(CKL_ERR_RUNTIME, "crackle_amd: out of host memory");

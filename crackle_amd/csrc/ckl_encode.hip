@@ -12,6 +12,7 @@
 //   stream assembly                                 src/crackle.hpp:171-216    host
 #include "ckl_encoder.hpp"
 #include "ckl_runs.hpp"
+#include "ckl_strips.hpp"
 #include "ckl_trail.hpp"
 
 #include <algorithm>
@@ -717,6 +718,29 @@ __global__ void __launch_bounds__(kBlock) k_mapping_comps(
 	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
 	if (c >= r.ncomp[zi]) return;
 	mapping[comp_off[zi] + c] = static_cast<uint64_t>(labels[zi * sxy + r.comp_pix[r.rbase[zi] + c]]);
+}
+
+// the encoder's strips (flat_enqueue): planes only, no record lists; seven workgroups per CU like k_strip_ccl
+// Tables of kEncStripCap runs, not kStripCap: the label stream runs beside two walks per CU and has kFlatResolveLds of
+// the CU's LDS (encode_typed: labels_at_walk).  Two of these workgroups fit into that, of the decoder's size only one:
+// at C2 (two walks of 58 KiB) the kernel took 0.79 ms with 2560 runs and the encode was slower than on the run pipeline;
+// with 2048, although the strips get 28 rows instead of 32, the encode's device time went from 2.72 to 2.56 ms.
+constexpr uint32_t kEncStripCap = 2048;
+constexpr size_t kFlatResolveLds = 40960;
+static_assert(2 * strip_ccl_words(kEncStripCap) * sizeof(uint32_t) <= kFlatResolveLds, "two strip workgroups beside two walks");
+__global__ void __launch_bounds__(kBlock, 7) k_strip_ccl_enc(RunGeom g, StripArrays sa, const uint32_t* __restrict__ G, uint32_t n_pixels) {
+	__shared__ __attribute__((aligned(16))) uint32_t s_lds[strip_ccl_words(kEncStripCap)];
+	strip_ccl_body<false, false, true, kEncStripCap>(g, sa, RecordLists{}, G, n_pixels, nullptr, blockIdx.y, blockIdx.x, s_lds);
+}
+
+// one thread per component: the slots of k_slice_resolve_enc -> the dense table (comp_off: the host's prefix of the
+// counts).  grid = (ceil(max components / kBlock), slices)
+__global__ void __launch_bounds__(kBlock) k_gather_slots(
+	const uint64_t* __restrict__ slots, uint32_t slot_cap, const uint32_t* __restrict__ ncomp, const uint64_t* __restrict__ comp_off, uint64_t* __restrict__ mapping
+) {
+	const uint32_t zi = blockIdx.y;
+	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+	if (c < ncomp[zi]) mapping[comp_off[zi] + c] = slots[static_cast<uint64_t>(zi) * slot_cap + c];
 }
 
 // Global component id of every voxel (cc3d.hpp:371-400 numbers components continuously
@@ -1709,14 +1733,33 @@ RunArrays flat_arrays(const ckl_encoder& e) {
 	return ra;
 }
 
-// encode_flat per-slice part (labels.hpp:56-88) on runs of the label planes: components
-// and their crc32c.  Enqueued on the label stream right after the planes exist; the
-// results are collected (flat_collect) while the crack trail runs on the other stream.
-void flat_enqueue(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
+// component counts, crc accumulators, id widths and error words of the slices lie side by side, the strip kernels' overflow
+// word behind them: flat_collect brings them back in ONE transfer (four separate round trips cost the label path 0.2 ms,
+// and it is what the encode ends with)
+void flat_report_layout(ckl_encoder& e, uint32_t ns, hipStream_t s) {
+	e.d_flat_report.ensure(4 * static_cast<size_t>(ns) + 1);
+	e.d_ncomp.borrow(e.d_flat_report.p, ns); e.d_crc_acc.borrow(e.d_flat_report.p + ns, ns);
+	e.d_idbits.borrow(e.d_flat_report.p + 2 * static_cast<size_t>(ns), ns); e.d_slice_err2.borrow(e.d_flat_report.p + 3 * static_cast<size_t>(ns), ns);
+	CKL_HIP(hipMemsetAsync(e.d_slice_err2.p, 0, (static_cast<size_t>(ns) + 1) * sizeof(uint32_t), s));      // the error words and the overflow word
+}
+
+// the label planes as the run and strip kernels read them
+RunGeom flat_geom(const ckl_encoder& e, int64_t sx, int64_t sy, uint32_t ns) {
+	RunGeom g;
+	g.planeV = plane_v(e); g.planeH = plane_h(e, ns);
+	g.row_words = e.row_words; g.plane_words = e.plane_words;
+	g.flip = 1u;   // a set bit (labels differ) is a break, whatever the stream's crack format
+	g.sx = static_cast<uint32_t>(sx); g.sy = static_cast<uint32_t>(sy);
+	return g;
+}
+
+// encode_flat per-slice part (labels.hpp:56-88) on runs of the label planes, the general pipeline of ckl_runs.hpp:
+// components and their crc32c from one table entry per run.  It serves what the strip kernels below do not take.
+void flat_enqueue_runs(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
 	hipStream_t s = e.stream2;
 	const uint32_t ns = static_cast<uint32_t>(sz);
 	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	ensure_geom_table(e, sxy);
+	e.flat_strips = false;
 
 	// a run starts at x = 0 of every row and wherever the left neighbour differs
 	// (the host tables stay alive in the session: nothing here waits for the uploads)
@@ -1733,19 +1776,10 @@ void flat_enqueue(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
 	upload(e.d_rbase, rbase, s); upload(e.d_rcap, rcap, s);
 	e.d_word_base.ensure(e.plane_words * ns);
 	e.d_parent.ensure(rtot); e.d_run_start.ensure(rtot); e.d_run_cc.ensure(rtot); e.d_comp_pix.ensure(rtot);
-	// component counts, crc accumulators, id widths and error words of the slices lie side by side: flat_collect brings
-	// them back in ONE transfer (four separate round trips cost the label path 0.2 ms, and it is what the encode ends with)
 	e.d_nruns.ensure(ns);
-	e.d_flat_report.ensure(4 * static_cast<size_t>(ns));
-	e.d_ncomp.borrow(e.d_flat_report.p, ns); e.d_crc_acc.borrow(e.d_flat_report.p + ns, ns);
-	e.d_idbits.borrow(e.d_flat_report.p + 2 * static_cast<size_t>(ns), ns); e.d_slice_err2.borrow(e.d_flat_report.p + 3 * static_cast<size_t>(ns), ns);
-	CKL_HIP(hipMemsetAsync(e.d_slice_err2.p, 0, ns * sizeof(uint32_t), s));
+	flat_report_layout(e, ns, s);
 
-	RunGeom g;
-	g.planeV = plane_v(e); g.planeH = plane_h(e, ns);
-	g.row_words = e.row_words; g.plane_words = e.plane_words;
-	g.flip = 1u;   // a set bit (labels differ) is a break, whatever the stream's crack format
-	g.sx = static_cast<uint32_t>(sx); g.sy = static_cast<uint32_t>(sy);
+	const RunGeom g = flat_geom(e, sx, sy, ns);
 	const RunArrays ra = flat_arrays(e);
 	hipLaunchKernelGGL(k_run_index, dim3(ns), dim3(kIndexBlock), 0, s, g, ra);
 	launch_run_union(s, ns, g, ra);
@@ -1755,7 +1789,105 @@ void flat_enqueue(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
 	e.d_blk_roots.ensure(static_cast<size_t>(rs.nblk) * ns);
 	rs.run_local = e.d_run_local.p; rs.blk_roots = e.d_blk_roots.p;
 	launch_run_resolve(s, ns, ra, rs, e.d_G.p, static_cast<uint32_t>(sxy), 0u, e.d_crc_acc.p, e.d_idbits.p);
-	HT_MARK("f:enqueue");
+	HT_MARK("f:enqueue_runs");
+}
+
+// k_slice_resolve_enc's table: the label stream runs beside two walks per CU and keeps to the 40 KiB that
+// labels_at_walk (encode_typed) leaves it; a slice with more strip components gets a CU's LDS (flat_collect)
+uint32_t flat_resolve_cap(size_t lds_bytes) {
+	uint32_t cap = static_cast<uint32_t>(std::min<size_t>(kResolveCap, (lds_bytes - (kMaxStrips + 64u) * 4u) / 4u));
+	if (const char* env = getenv("CKL_ENC_RESOLVE_CAP")) cap = std::min<uint32_t>(cap, static_cast<uint32_t>(std::max(1, atoi(env))));      // testing: forces the hand-over
+	return cap;
+}
+uint32_t flat_resolve_cap_max(ckl_encoder& e) {
+	if (!e.max_lds) CKL_HIP(hipDeviceGetAttribute(&e.max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
+	return flat_resolve_cap(static_cast<size_t>(e.max_lds) - 8192u);
+}
+
+// Can the strip kernels label this volume, and with what strips?  The host knows every slice's run count: the strips
+// are sized from the densest slice, the decoder's rule (decoder_build) with the true density instead of an estimate
+// and the encoder's table size (kEncStripCap).
+// Not theirs: rows wider than a strip, more strips than the resolve takes, a densest slice of which not one row fits
+// a strip, and a slice that must have more components than the largest resolve table holds (every component has a run
+// that nothing joins to the row above: at least runs minus vertically equal pixel pairs) — noise pays nothing extra.
+bool flat_strip_plan(ckl_encoder& e, int64_t sx, int64_t sy, uint32_t ns) {
+	if (getenv("CKL_ENC_LABEL_RUNS")) return false;      // A/B and tests: the run pipeline for everything
+	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
+	if (e.row_words == 0 || e.row_words > kStripWords || sxy >= 0xFFFF0000ull) return false;
+	uint64_t runs_max = 0, comps_min = 0;
+	const uint64_t pairs_up = static_cast<uint64_t>(sx) * (sy - 1);
+	for (uint32_t zi = 0; zi < ns; zi++) {
+		const uint64_t runs = static_cast<uint64_t>(sy) + e.count_v[zi];
+		const uint64_t equal_up = pairs_up - std::min<uint64_t>(pairs_up, e.count_h[zi]);
+		runs_max = std::max<uint64_t>(runs_max, runs);
+		comps_min = std::max<uint64_t>(comps_min, runs > equal_up ? runs - equal_up : 0ull);
+	}
+	const double runs_per_row = static_cast<double>(runs_max) / static_cast<double>(sy);
+	const uint32_t fit = static_cast<uint32_t>(0.7 * kEncStripCap / runs_per_row);
+	if (fit < 1u) return false;
+	const uint32_t rows = std::max<uint32_t>(1u, std::min<uint32_t>(kStripWords / e.row_words, fit));
+	const uint32_t nstrips = (static_cast<uint32_t>(sy) + rows - 1) / rows;
+	if (nstrips > kMaxStrips || comps_min > flat_resolve_cap_max(e)) return false;
+	e.flat_strip_rows = rows; e.flat_nstrips = nstrips;
+	e.flat_strip_cap = static_cast<uint32_t>(std::min<uint64_t>(kEncStripCap, static_cast<uint64_t>(rows) * sx));
+	if (const char* env = getenv("CKL_ENC_STRIP_CAP")) e.flat_strip_cap = std::min<uint32_t>(e.flat_strip_cap, static_cast<uint32_t>(std::max(1, atoi(env))));      // testing: strips overflow
+	return true;
+}
+
+StripArrays flat_strip_arrays(const ckl_encoder& e) {
+	StripArrays sa = {};
+	sa.run_lid = e.s_run_lid.p; sa.sc_w = e.s_sc_w.p; sa.sc_cc = e.s_sc_first.p;
+	sa.strip_nruns = e.s_strip_nruns.p; sa.strip_nsc = e.s_strip_nsc.p;
+	sa.seam_first = e.s_seam_first.p; sa.seam_last = e.s_seam_last.p;
+	sa.slice_err = e.d_slice_err2.p; sa.overflow = e.d_flat_report.p + 4 * e.d_ncomp.n;
+	sa.nstrips = e.flat_nstrips; sa.strip_rows = e.flat_strip_rows; sa.cap = e.flat_strip_cap; sa.zbase = 0;
+	return sa;
+}
+
+// k_slice_resolve_enc over all slices with a table of `cap` entries
+void flat_launch_resolve(ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, uint32_t ns, uint32_t cap) {
+	hipStream_t s = e.stream2;
+	e.flat_resolve_cap = cap;
+	e.d_label_slots.ensure(static_cast<size_t>(ns) * cap);
+	ResolveArgs ra = {};
+	ra.cap = cap;
+	EncResolve en;
+	en.labels = labels; en.sxy = static_cast<uint64_t>(sx) * sy; en.slots = e.d_label_slots.p; en.crc_acc = e.d_crc_acc.p; en.idbits = e.d_idbits.p;
+	const RunGeom g = flat_geom(e, sx, sy, ns);
+	const StripArrays sa = flat_strip_arrays(e);
+	const size_t tab_bytes = static_cast<size_t>(cap) * sizeof(uint32_t);
+	with_label_type(e.dtype_bytes, [&](auto t) {
+		typedef typename decltype(t)::type LABEL;
+		if (tab_bytes > 48u * 1024u) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slice_resolve_enc<LABEL>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tab_bytes)));
+		hipLaunchKernelGGL(k_slice_resolve_enc<LABEL>, dim3(ns), dim3(kResolveBlock), tab_bytes, s, g, sa, ra, en, e.d_ncomp.p);
+	});
+}
+
+// The label stage of a volume (labels.hpp:56-88): the 2-D components of every slice, their count, the crc32c of the
+// component image and the label of every component.  Enqueued on the label stream; the results are collected
+// (flat_collect) while the crack trail runs on the other stream.  Flat labels come from the strip kernels
+// (ckl_strips.hpp): k_strip_ccl_enc labels each strip of rows in LDS, k_slice_resolve_enc joins the strips of a slice —
+// tables per strip component, not per run.  need_runs: the caller reads the run tables afterwards (pins and
+// ckl_encoder_components paint the component volume from run_cc); those and what flat_strip_plan turns down take the
+// run pipeline.
+// beside_walk: the stage starts with the trail's serial walk, which leaves the chip to it.  Only then do the strips take
+// it: in front of the graph kernel (large slices, many nodes) the strip kernel shares the chip with kernels that fill it,
+// and the trail paid for it in full when that was tried at C2; those volumes stay as they were.
+void flat_enqueue(ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, int64_t sz, bool need_runs, bool beside_walk) {
+	hipStream_t s = e.stream2;
+	const uint32_t ns = static_cast<uint32_t>(sz);
+	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
+	ensure_geom_table(e, sxy);
+	if (need_runs || !beside_walk || !flat_strip_plan(e, sx, sy, ns)) { flat_enqueue_runs(e, sx, sy, sz); return; }
+	e.flat_strips = true;
+	const size_t nst = static_cast<size_t>(e.flat_nstrips) * ns;
+	e.s_strip_nruns.ensure(nst); e.s_strip_nsc.ensure(nst);
+	e.s_seam_first.ensure(nst * e.row_words); e.s_seam_last.ensure(nst * e.row_words);
+	e.s_run_lid.ensure(nst * e.flat_strip_cap); e.s_sc_w.ensure(nst * e.flat_strip_cap); e.s_sc_first.ensure(nst * e.flat_strip_cap);
+	flat_report_layout(e, ns, s);
+	hipLaunchKernelGGL(k_strip_ccl_enc, dim3(e.flat_nstrips, ns), dim3(kBlock), 0, s, flat_geom(e, sx, sy, ns), flat_strip_arrays(e), e.d_G.p, static_cast<uint32_t>(sxy));
+	flat_launch_resolve(e, labels, sx, sy, ns, flat_resolve_cap(kFlatResolveLds));
+	HT_MARK("f:enqueue_strips");
 }
 
 // component counts, crcs, component -> label (labels.hpp:71-88)
@@ -1764,11 +1896,25 @@ void flat_collect(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	hipStream_t s = e.stream2;
 	const uint32_t ns = static_cast<uint32_t>(sz);
 	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	// laid out by flat_enqueue: ncomp | crc_acc | idbits | slice_err2, one transfer
-	const std::vector<uint32_t> rep = download(e.d_flat_report.p, 4 * static_cast<size_t>(ns), s);
+	// laid out by flat_report_layout: ncomp | crc_acc | idbits | slice_err2 | overflow, one transfer
+	const size_t rep_n = 4 * static_cast<size_t>(ns) + 1;
+	std::vector<uint32_t> rep = download(e.d_flat_report.p, rep_n, s);
+	if (e.flat_strips && rep[rep_n - 1] == 2u && e.flat_resolve_cap < flat_resolve_cap_max(e)) {
+		// only k_slice_resolve_enc's table was too small, and it can be larger (over-segmented slices): once more with a
+		// CU's LDS per slice, as the decoder does; the strips' tables stand
+		CKL_HIP(hipMemsetAsync(e.d_flat_report.p + rep_n - 1, 0, sizeof(uint32_t), s));
+		flat_launch_resolve(e, labels, sx, sy, ns, flat_resolve_cap_max(e));
+		HT_MARK("f:resolve_retry");
+		rep = download(e.d_flat_report.p, rep_n, s);
+	}
+	if (e.flat_strips && rep[rep_n - 1]) {
+		// a strip or a resolve table overflowed: the whole volume again on the run pipeline
+		flat_enqueue_runs(e, sx, sy, sz);
+		rep = download(e.d_flat_report.p, rep_n, s);
+	}
 	const uint32_t *acc = rep.data() + ns, *idbits = rep.data() + 2 * static_cast<size_t>(ns), *errs = rep.data() + 3 * static_cast<size_t>(ns);
 	out.ncomp.assign(rep.begin(), rep.begin() + ns);
-	HT_MARK("f:wait");
+	HT_MARK(e.flat_strips ? "f:wait_strips" : "f:wait_runs");
 	for (uint32_t zi = 0; zi < ns; zi++) if (errs[zi]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: run table overflow on z=" + std::to_string(zi));
 	const uint32_t init_term = gf_mul(0xFFFFFFFFu, gf_xpow(32ull * sxy));
 	out.crcs.resize(ns);
@@ -1778,17 +1924,18 @@ void flat_collect(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 		out.crcs[zi] = ~(gf_mul(acc[zi], fix) ^ init_term);
 	}
 
-	std::vector<uint64_t> comp_off(ns);
+	// (the offsets stay alive in the session: nothing here waits for their upload)
+	std::vector<uint64_t>& comp_off = e.h_comp_off;
+	comp_off.assign(ns, 0);
 	uint64_t total = 0;
 	for (uint32_t zi = 0; zi < ns; zi++) { comp_off[zi] = total; total += out.ncomp[zi]; }
 	upload(e.d_comp_off, comp_off, s);
 	e.d_mapping.ensure(total + 1);
-	const RunArrays ra = flat_arrays(e);
 	uint32_t max_ncomp = 1;
 	for (uint32_t zi = 0; zi < ns; zi++) max_ncomp = std::max(max_ncomp, out.ncomp[zi]);
-	hipLaunchKernelGGL(k_mapping_comps<LABEL>, dim3((max_ncomp + kBlock - 1) / kBlock, ns), dim3(kBlock), 0, s,
-		labels, ra, sxy, e.d_comp_off.p, e.d_mapping.p);
-	CKL_HIP(hipStreamSynchronize(s));   // comp_off (pageable) must be consumed before it goes out of scope
+	const dim3 grid((max_ncomp + kBlock - 1) / kBlock, ns);
+	if (e.flat_strips) hipLaunchKernelGGL(k_gather_slots, grid, dim3(kBlock), 0, s, e.d_label_slots.p, e.flat_resolve_cap, e.d_ncomp.p, e.d_comp_off.p, e.d_mapping.p);
+	else hipLaunchKernelGGL(k_mapping_comps<LABEL>, grid, dim3(kBlock), 0, s, labels, flat_arrays(e), sxy, e.d_comp_off.p, e.d_mapping.p);
 	out.total = total;
 }
 
@@ -1963,7 +2110,8 @@ void encode_typed(
 	// counts are known).  (The sharded encode's label stream also carries the ranks' exchange of unique
 	// labels: 0.5 ms on the host.  It fits since the slab's labels are exchanged unsorted.)
 	bool labels_at_walk = false;
-	if (labels_first && !graph_done) flat_enqueue(e, sx, sy, sz);
+	const bool need_runs = head.label_format != FLAT;      // pins paint the component volume from the run tables
+	if (labels_first && !graph_done) flat_enqueue(e, labels, sx, sy, sz, need_runs, false);
 	const bool trail_cached = !graph_done && have_planes && ov && ov->has_model && head.markov_model_order > 0 && e.trail_for == static_cast<const void*>(labels)
 		&& e.trail_perm == (head.crack_format == PERMISSIBLE) && e.trail_order == head.markov_model_order;
 	e.trail_for = nullptr;
@@ -1975,8 +2123,8 @@ void encode_typed(
 		for (uint32_t v : e.count_special) max_special = std::max(max_special, v);
 		int max_lds = 0;
 		CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
-		labels_at_walk = max_special < 5000 && 2 * trail_walk_lds(max_special) + 40960 <= static_cast<size_t>(max_lds);
-		if (!labels_at_walk) flat_enqueue(e, sx, sy, sz);
+		labels_at_walk = max_special < 5000 && 2 * trail_walk_lds(max_special) + kFlatResolveLds <= static_cast<size_t>(max_lds);
+		if (!labels_at_walk) flat_enqueue(e, labels, sx, sy, sz, need_runs, false);
 	}
 
 	const bool permissible = head.crack_format == PERMISSIBLE;
@@ -2024,7 +2172,7 @@ void encode_typed(
 	auto label_side = [&]() {
 		if (labels_at_walk) {
 			CKL_HIP(hipStreamWaitEvent(s2, e.evd0, 0));      // (starting one kernel earlier, beside k_trail_components, cost 0.2 ms)
-			flat_enqueue(e, sx, sy, sz);
+			flat_enqueue(e, labels, sx, sy, sz, need_runs, true);
 		}
 		flat_collect<LABEL>(e, labels, sx, sy, sz, fr);
 		HT_MARK("flat");
@@ -2460,7 +2608,7 @@ static uint32_t* encoder_components(ckl_encoder* e, const void* labels_device, i
 	if (voxels == 0) return cc_device;
 	FlatResult fr;
 	if (!planes_cached(*e, labels_device, sx, sy, sz)) planes_pass_any(*e, labels_device, sx, sy, sz, nullptr);
-	flat_enqueue(*e, sx, sy, sz);
+	flat_enqueue(*e, labels_device, sx, sy, sz, true, false);      // (the paint below reads the run tables)
 	with_label_type(e->dtype_bytes, [&](auto t) { flat_collect(*e, static_cast<const typename decltype(t)::type*>(labels_device), sx, sy, sz, fr); });
 	if (fr.total + id_base > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
 	hipStream_t s2 = e->stream2;

@@ -57,7 +57,7 @@ struct ckl_encoder {
 	DevBuf<uint32_t> d_rcap, d_word_base, d_parent, d_run_start, d_run_cc, d_comp_pix, d_nruns, d_ncomp, d_idbits, d_blk_roots;
 	DevBuf<uint16_t> d_run_local;
 	DevBuf<uint32_t> d_G, d_crc_acc;
-	DevBuf<uint32_t> d_flat_report;     // [4][nslices]: ncomp | crc_acc | idbits | slice_err2 (views above)
+	DevBuf<uint32_t> d_flat_report;     // [4][nslices] + 1: ncomp | crc_acc | idbits | slice_err2 (views above) | the strip kernels' overflow word
 	uint64_t g_table_pixels = 0;                // slice size the G table was built for
 	DevBuf<uint64_t> d_mapping, d_sorted, d_uniq, d_label_hash, d_label_list;
 	DevBuf<uint32_t> d_cc_volume;                // global component id of every voxel (pin encoding only)
@@ -78,6 +78,15 @@ struct ckl_encoder {
 	int64_t planes_dims[3] = { 0, 0, 0 };
 	std::vector<uint64_t> h_rbase;
 	std::vector<uint32_t> h_rcap;
+	std::vector<uint64_t> h_comp_off;  // first component of every slice: stays alive while its upload is in flight
+	// flat labels from the strip kernels (ckl_strips.hpp; flat_enqueue / flat_collect): per-strip tables, then the labels
+	// of every slice's components in a slot of flat_resolve_cap entries
+	DevBuf<uint16_t> s_run_lid, s_seam_first, s_seam_last;
+	DevBuf<uint32_t> s_sc_w, s_sc_first, s_strip_nruns, s_strip_nsc;
+	DevBuf<uint64_t> d_label_slots;
+	uint32_t flat_nstrips = 0, flat_strip_rows = 0, flat_strip_cap = 0, flat_resolve_cap = 0;
+	int max_lds = 0;                   // the device's LDS per workgroup (asked once)
+	bool flat_strips = false;          // the label stage that is enqueued runs on the strip kernels
 	// trail graph (ckl_trail.hpp)
 	std::vector<uint32_t> count_special, count_corner;
 	DevBuf<uint32_t> d_plane_partial, t_blk_special, t_blk_corner;

@@ -43,7 +43,7 @@ struct StripArrays {
 	// give every strip a fixed slot of `cap` entries, so that no kernel waits for another's counts
 	uint16_t* run_lid;         // [strips][cap] strip-local component of each run
 	uint32_t* sc_w;            // [strips][cap] per strip component: XOR of its runs' crc weights
-	uint32_t* sc_cc;           // [strips][cap] per strip component: component id of the slice (pins)
+	uint32_t* sc_cc;           // [strips][cap] per strip component: component id of the slice (pins); the encoder's variant keeps the component's first pixel here
 	void* sc_label;            // [strips][cap] per strip component: label, typed like the output
 	uint32_t* strip_nruns;     // [strips] (kStripOverflow: the strip did not fit)
 	uint32_t* strip_nsc;       // [strips] strip components
@@ -175,22 +175,29 @@ __device__ __forceinline__ void raster_half_record(
 // k_slice_resolve read them there); otherwise they are read from the planes k_decode_cracks left.
 // The body works in `lds` (kStripCclWords 32-bit words, 16-byte aligned) on strip k of slice zi, so that
 // the caller owns the block (a launch mixing stages of different slice groups was tried: DESIGN.md section 10).
-constexpr uint32_t kStripCclWords = (kStripCap + kStripEdgeCap + kStripWords / 2 + 2 * kStripBitmapWords + kWaves + 2 + 7) & ~7u;
-template <bool DIAG, bool RECORDS>
+// ENC: the encoder's variant (k_strip_ccl_enc, ckl_encode.hip) — the first pixel of every strip component (slice-linear: the start of
+// its root run, the first of its runs) goes to sc_cc, where the resolve finds the component's label; row_run, which
+// only pins and the paint read, is not written.
+// CAP: runs the tables hold (the encoder's strips share a CU's LDS with the crack trail's walk and take smaller ones)
+constexpr uint32_t strip_ccl_words(uint32_t cap) { return (cap + (kStripWords + cap / 2) + kStripWords / 2 + 2 * (cap / 32) + kWaves + 2 + 7) & ~7u; }
+constexpr uint32_t kStripCclWords = strip_ccl_words(kStripCap);
+template <bool DIAG, bool RECORDS, bool ENC = false, uint32_t CAP = kStripCap>
 __device__ __forceinline__ void strip_ccl_body(
 	const RunGeom& g, const StripArrays& sa, const RecordLists& rl, const uint32_t* __restrict__ G, uint32_t n_pixels, unsigned long long* __restrict__ diag,
 	uint32_t zi, uint32_t k, uint32_t* lds
 ) {
+	constexpr uint32_t kRunsPerThread = CAP / kBlock, kBitmapWords = CAP / 32, kEdgeCap = kStripWords + CAP / 2;
+	static_assert(CAP % kBlock == 0 && CAP % 64 == 0 && CAP <= kStripCap, "whole runs per thread, whole bitmap words");
 	uint32_t* s_parent = lds;                         // union-find, then the crc weights per strip component (RECORDS: first the piece of plane H)
-	uint32_t* s_mem = s_parent + kStripCap;           // s_b | s_pool, and over both of them the edge list of the unions
-	uint16_t* s_wb = reinterpret_cast<uint16_t*>(s_mem + kStripEdgeCap);          // runs before each word
+	uint32_t* s_mem = s_parent + CAP;           // s_b | s_pool, and over both of them the edge list of the unions
+	uint16_t* s_wb = reinterpret_cast<uint16_t*>(s_mem + kEdgeCap);          // runs before each word
 	uint32_t* s_b = s_mem;                                                        // break words of the strip
 	uint16_t* s_pool = reinterpret_cast<uint16_t*>(s_mem + kStripWords);          // first pixel of each run (relative to the strip), later its strip component
-	uint32_t* s_bm = s_mem + kStripEdgeCap + kStripWords / 2;
-	uint32_t* s_bmbase = s_bm + kStripBitmapWords;
-	uint32_t* s_scan = s_bmbase + kStripBitmapWords;
+	uint32_t* s_bm = s_mem + kEdgeCap + kStripWords / 2;
+	uint32_t* s_bmbase = s_bm + kBitmapWords;
+	uint32_t* s_scan = s_bmbase + kBitmapWords;
 	uint32_t* s_misc = s_scan + kWaves;
-	static_assert((kStripCap * 4) % 16 == 0 && (kStripEdgeCap * 4) % 16 == 0, "tables stay 16-byte aligned");
+	static_assert((CAP * 4) % 16 == 0 && (kEdgeCap * 4) % 16 == 0, "tables stay 16-byte aligned");
 	unsigned long long d_t = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
 	auto stamp = [&](int slot) {
 		if (DIAG && threadIdx.x == 0) {
@@ -212,7 +219,7 @@ __device__ __forceinline__ void strip_ccl_body(
 	if (RECORDS) {
 		// the strip's records -> its pieces of the two planes, in LDS (s_mem: plane V, later the break
 		// words; s_parent: plane H, dead once the words are in registers)
-		static_assert(kStripCap >= kStripWords, "plane H piece is built in the union-find table");
+		static_assert(CAP >= kStripWords, "plane H piece is built in the union-find table");
 		uint32_t* sV = s_mem;
 		uint32_t* sH = s_parent;
 		const uint32_t n_rec = min(rl.count[si], rl.cap);
@@ -303,17 +310,20 @@ __device__ __forceinline__ void strip_ccl_body(
 		}
 	}
 	for (uint32_t j = t; j < nloc; j += kBlock) s_parent[j] = j;
-	if (t < kStripBitmapWords) s_bm[t] = 0u;
+	if (t < kBitmapWords) s_bm[t] = 0u;
 	__syncthreads();
 	stamp(1);
 	// the crc weights of my runs are requested now and collected after the unions
-	uint32_t gv[kStripRunsPerThread];
+	uint32_t gv[kRunsPerThread];
+	uint32_t first_px[ENC ? (kRunsPerThread + 1) / 2 : 1] = {};      // ENC: my runs' first pixels, two to a register (the pool is reused below)
 	{
 		const uint32_t p0 = y0 * g.sx;
 #pragma unroll
-		for (uint32_t i = 0; i < kStripRunsPerThread; i++) {
+		for (uint32_t i = 0; i < kRunsPerThread; i++) {
 			const uint32_t j = t + i * kBlock;
-			gv[i] = G[n_pixels - (p0 + s_pool[j < nloc ? j : 0u])];
+			const uint32_t px = s_pool[j < nloc ? j : 0u];
+			gv[i] = G[n_pixels - (p0 + px)];
+			if (ENC) first_px[i >> 1] |= px << (16u * (i & 1u));
 		}
 	}
 	// per-row and seam tables
@@ -325,7 +335,7 @@ __device__ __forceinline__ void strip_ccl_body(
 			if (j && w[j] == 0) yy++;
 			if (wl >= nw) break;
 			const uint16_t wbv = s_wb[wl];
-			if (w[j] == 0) sa.row_run[static_cast<uint64_t>(zi) * g.sy + y0 + yy] = wbv;      // (pins look pixels up)
+			if (!ENC && w[j] == 0) sa.row_run[static_cast<uint64_t>(zi) * g.sy + y0 + yy] = wbv;      // (pins look pixels up)
 			if (wl < rw) sa.seam_first[static_cast<uint64_t>(si) * rw + wl] = wbv;
 			if (wl + rw >= nw) sa.seam_last[static_cast<uint64_t>(si) * rw + (wl + rw - nw)] = wbv;
 		}
@@ -347,7 +357,7 @@ __device__ __forceinline__ void strip_ccl_body(
 		uint32_t ve[1] = { n_e }, te[1];
 		block_excl_add<1>(ve, te, s_scan);      // its barriers: every read of s_b / s_pool is done
 		const uint32_t n_edges = te[0];
-		if (n_edges <= kStripEdgeCap) {      // uniform
+		if (n_edges <= kEdgeCap) {      // uniform
 			uint32_t at = ve[0];
 #pragma unroll
 			for (uint32_t j = 0; j < 4; j++) {
@@ -372,23 +382,23 @@ __device__ __forceinline__ void strip_ccl_body(
 	__syncthreads();      // the pool now takes the strip components
 	stamp(2);
 	// ---- roots -> strip-local component ids in run order
-	uint32_t root[kStripRunsPerThread];
+	uint32_t root[kRunsPerThread];
 #pragma unroll
-	for (uint32_t i = 0; i < kStripRunsPerThread; i++) {
+	for (uint32_t i = 0; i < kRunsPerThread; i++) {
 		const uint32_t j = t + i * kBlock;
 		root[i] = j < nloc ? sm_find(s_parent, j) : 0u;
 		if (j < nloc && root[i] == j) atomicOr(s_bm + (j >> 5), 1u << (j & 31u));
 	}
 	__syncthreads();
 	if (t < kWave) {
-		static_assert(kStripBitmapWords <= 2 * kWave, "two bitmap words per lane");
-		const uint32_t c0 = t < kStripBitmapWords ? __popc(s_bm[t]) : 0u;
-		const uint32_t c1 = t + kWave < kStripBitmapWords ? __popc(s_bm[t + kWave]) : 0u;
+		static_assert(kBitmapWords <= 2 * kWave, "two bitmap words per lane");
+		const uint32_t c0 = t < kBitmapWords ? __popc(s_bm[t]) : 0u;
+		const uint32_t c1 = t + kWave < kBitmapWords ? __popc(s_bm[t + kWave]) : 0u;
 		const uint32_t i0 = wave_incl_add(c0);
 		const uint32_t tot0 = __shfl(i0, kWave - 1, kWave);
 		const uint32_t i1 = wave_incl_add(c1);
-		if (t < kStripBitmapWords) s_bmbase[t] = i0 - c0;
-		if (t + kWave < kStripBitmapWords) s_bmbase[t + kWave] = tot0 + i1 - c1;
+		if (t < kBitmapWords) s_bmbase[t] = i0 - c0;
+		if (t + kWave < kBitmapWords) s_bmbase[t + kWave] = tot0 + i1 - c1;
 		if (t == kWave - 1) s_misc[1] = tot0 + i1;
 	}
 	__syncthreads();
@@ -398,7 +408,7 @@ __device__ __forceinline__ void strip_ccl_body(
 	uint16_t* lid_out = sa.run_lid + slot;
 	const bool narrow = nsc <= 256u;
 #pragma unroll
-	for (uint32_t i = 0; i < kStripRunsPerThread; i++) {
+	for (uint32_t i = 0; i < kRunsPerThread; i++) {
 		const uint32_t j = t + i * kBlock;
 		if (j >= nloc) break;
 		const uint32_t r = root[i];
@@ -406,13 +416,14 @@ __device__ __forceinline__ void strip_ccl_body(
 		s_pool[j] = static_cast<uint16_t>(lid);
 		if (narrow) reinterpret_cast<uint8_t*>(lid_out)[j] = static_cast<uint8_t>(lid);
 		else lid_out[j] = static_cast<uint16_t>(lid);
+		if (ENC && r == j) sa.sc_cc[slot + lid] = y0 * g.sx + ((first_px[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu);
 	}
 	for (uint32_t j = t; j < nsc; j += kBlock) s_parent[j] = 0u;      // every find is done: the table becomes the weights
 	__syncthreads();
 	stamp(3);
 	// ---- crc weights: run j covering [a_j, a_j+1) adds G[n - a_j] ^ G[n - a_j+1] to its component
 #pragma unroll
-	for (uint32_t i = 0; i < kStripRunsPerThread; i++) {
+	for (uint32_t i = 0; i < kRunsPerThread; i++) {
 		const uint32_t j = t + i * kBlock;
 		if (j >= nloc) break;
 		atomicXor(s_parent + s_pool[j], gv[i]);
@@ -452,6 +463,19 @@ struct ResolveArgs {
 	uint32_t host_flags_n;           // slices of the session (index of the first overflow word)
 };
 
+// what the encoder's resolve (k_slice_resolve_enc) writes instead of checking a stored count and crc: the slice's
+// component count goes to ncomp_out as always, the raw crc accumulator (over kEncIdBits bits of every id: the host
+// applies x^(32 - idbits), as it does for the run pipeline) and the id width to the report, and the label of every
+// component — read at its first pixel — to the slice's slot of ra.cap entries
+constexpr uint32_t kEncIdBits = 16;      // ids are below kResolveCap
+struct EncResolve {
+	const void* labels;        // the volume, typed like OUT
+	uint64_t sxy;
+	uint64_t* slots;           // [nslices][ra.cap]
+	uint32_t* crc_acc;         // [nslices]
+	uint32_t* idbits;          // [nslices]
+};
+
 // little-endian integer of W bytes at any address (global memory takes unaligned accesses: one load, not W)
 template <int W>
 __device__ __forceinline__ uint64_t ld_le(const uint8_t* p) {
@@ -481,10 +505,11 @@ __device__ __forceinline__ void with_width(uint32_t w, F&& f) {
 // workgroups of 1024 share a CU (<= 64 registers) and all slices of a 512-slice volume run at once.
 // The body works on slice zi with its tables in the caller's LDS (s_tab: ra.cap entries, s_scbase: nstrips + 1,
 // s_scan: kResolveBlock / 64, s_flag: 1).  Returns false when the slice does not fit.
-template <typename OUT, bool LABELS, bool DIAG>
+// ENC: the encoder's mode (EncResolve above); OUT is then the volume's label type and LABELS is false.
+template <typename OUT, bool LABELS, bool DIAG, bool ENC = false>
 __device__ __forceinline__ bool slice_resolve_body(
 	const RunGeom& g, const StripArrays& sa, const ResolveArgs& ra, uint32_t* __restrict__ ncomp_out, unsigned long long* __restrict__ diag,
-	uint32_t zi, uint32_t* s_tab, uint32_t* s_scbase, uint32_t* s_scan, uint32_t* s_flag_p
+	uint32_t zi, uint32_t* s_tab, uint32_t* s_scbase, uint32_t* s_scan, uint32_t* s_flag_p, const EncResolve* en = nullptr
 ) {
 	uint32_t& s_flag = *s_flag_p;
 	static_assert(kResolveCap <= 0xFFFFu, "index and rank share a table entry");
@@ -572,11 +597,18 @@ __device__ __forceinline__ bool slice_resolve_body(
 	}
 	__syncthreads();
 	stamp(1);
-	// ---- every entry -> its root (a racing find only ever meets ancestors); the roots ranked in index order =
-	// raster order of the components' first pixels
+	// ---- every entry -> its root; the roots ranked in index order = raster order of the components' first pixels.
+	// The walk up stores nothing but the entry's own root: sm_find's path halving also writes the entries it passes,
+	// and such a write — an ancestor read before the entry's owner stored the root — could land after the owner's and
+	// leave the entry pointing at a non-root, whose rank field is 0 (seen as one wrong slice crc in ~16 000 slices
+	// whose strip components chain over many seams).  A racing reader only ever meets ancestors.
 	const uint32_t per = (total + kResolveBlock - 1) / kResolveBlock;      // <= kResolvePer
 	const uint32_t i0 = min(total, t * per), i1 = min(total, i0 + per);
-	for (uint32_t i = i0; i < i1; i++) sm_store(s_tab, i, sm_find(s_tab, i));
+	for (uint32_t i = i0; i < i1; i++) {
+		uint32_t r = i;
+		for (uint32_t p = sm_load(s_tab, r); p != r; p = sm_load(s_tab, r)) r = p;
+		sm_store(s_tab, i, r);
+	}
 	__syncthreads();
 	uint32_t nroot = 0;
 	for (uint32_t i = i0; i < i1; i++) nroot += s_tab[i] == i ? 1u : 0u;
@@ -597,8 +629,9 @@ __device__ __forceinline__ bool slice_resolve_body(
 	__syncthreads();
 	stamp(2);
 	const uint32_t ncomp = tot2[0];
-	const uint32_t nexp = ra.ncomp_expect[zi];
-	const uint64_t coff = ra.comp_off[zi];
+	const uint32_t nexp = ENC ? 0u : ra.ncomp_expect[zi];
+	const uint64_t coff = ENC ? 0ull : ra.comp_off[zi];
+	const uint32_t idbits = ENC ? kEncIdBits : ra.idbits;
 	// ---- ids, labels, crc32c of the component image: four entries per round, their loads side by side
 	uint32_t part = 0;
 	uint32_t sidx = strip0;
@@ -615,10 +648,14 @@ __device__ __forceinline__ bool slice_resolve_body(
 			gi[q] = static_cast<uint64_t>(si0 + sq) * sa.cap + (ii - s_scbase[sq]);
 			cc[q] = s_tab[s_tab[ii] & 0xFFFFu] >> 16;
 			wgt[q] = sa.sc_w[gi[q]];
-			key[q] = 0;
+			key[q] = ENC ? sa.sc_cc[gi[q]] : 0u;      // (ENC: the first pixel of the entry's strip component)
 		}
 		uint64_t lab[kPer];
-		if (LABELS) {
+		if (ENC) {
+#pragma unroll
+			for (uint32_t q = 0; q < kPer; q++) lab[q] = static_cast<const OUT*>(en->labels)[zi * en->sxy + key[q]];
+		}
+		else if (LABELS) {
 			// keys of the four entries in one trip to memory, their labels in a second one (entries past the
 			// end and ids outside the label section read entry 0 and are set right afterwards)
 			with_width(ra.key_width, [&](auto W) {
@@ -637,7 +674,11 @@ __device__ __forceinline__ bool slice_resolve_body(
 #pragma unroll
 		for (uint32_t q = 0; q < kPer; q++) {
 			if (r0 + q >= i1) continue;
-			if (LABELS) {
+			if (ENC) {
+				// a root's first pixel is its component's: roots are the smallest index of their set
+				if ((s_tab[r0 + q] & 0xFFFFu) == r0 + q) en->slots[static_cast<uint64_t>(zi) * ra.cap + cc[q]] = lab[q];
+			}
+			else if (LABELS) {
 				uint64_t val = 0;
 				if (cc[q] < nexp && key[q] < ra.num_unique) {
 					val = lab[q];
@@ -649,7 +690,7 @@ __device__ __forceinline__ bool slice_resolve_body(
 			else sa.sc_cc[gi[q]] = cc[q];
 			// sum over set bits j < idbits of the id:  wgt * x^(idbits-1-j)
 			uint32_t wg = wgt[q];
-			for (int j = static_cast<int>(ra.idbits) - 1; j >= 0; j--) {
+			for (int j = static_cast<int>(idbits) - 1; j >= 0; j--) {
 				part ^= ((cc[q] >> j) & 1u) ? wg : 0u;
 				wg = (wg >> 1) ^ ((wg & 1u) ? kCrcPoly : 0u);
 			}
@@ -661,12 +702,15 @@ __device__ __forceinline__ bool slice_resolve_body(
 	if (t == 0) {
 		uint32_t x = 0;
 		for (int wv = 0; wv < NW; wv++) x ^= s_scan[wv];
-		uint32_t e = 0;
-		if (ncomp != nexp) e |= ERR_NCOMP;
-		else if (ra.check_crc && gf_mul(x, ra.crc_fix) != ra.crc_expect[zi]) e |= ERR_CRC;
-		if (e) atomicOr(sa.slice_err + zi, e);
-		ncomp_out[zi] = ncomp;
-		if (ra.host_flags) ra.host_flags[zi] = sa.slice_err[zi] | e;      // (the bits of the kernels in front crossed a kernel boundary)
+		if (ENC) { ncomp_out[zi] = ncomp; en->crc_acc[zi] = x; en->idbits[zi] = kEncIdBits; }
+		else {
+			uint32_t e = 0;
+			if (ncomp != nexp) e |= ERR_NCOMP;
+			else if (ra.check_crc && gf_mul(x, ra.crc_fix) != ra.crc_expect[zi]) e |= ERR_CRC;
+			if (e) atomicOr(sa.slice_err + zi, e);
+			ncomp_out[zi] = ncomp;
+			if (ra.host_flags) ra.host_flags[zi] = sa.slice_err[zi] | e;      // (the bits of the kernels in front crossed a kernel boundary)
+		}
 	}
 	stamp(3);
 	return true;
@@ -679,6 +723,16 @@ static __global__ void __launch_bounds__(kResolveBlock, 8) k_slice_resolve(RunGe
 	__shared__ uint32_t s_scan[kResolveBlock / kWave];
 	__shared__ uint32_t s_flag;
 	slice_resolve_body<OUT, LABELS, DIAG>(g, sa, ra, ncomp_out, diag, blockIdx.x + sa.zbase, s_tab, s_scbase, s_scan, &s_flag);
+}
+
+// the encoder's resolve: grid = slices, block = kResolveBlock, dynamic LDS = ra.cap entries
+template <typename LABEL>
+static __global__ void __launch_bounds__(kResolveBlock, 8) k_slice_resolve_enc(RunGeom g, StripArrays sa, ResolveArgs ra, EncResolve en, uint32_t* __restrict__ ncomp_out) {
+	extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];      // ra.cap entries
+	__shared__ uint32_t s_scbase[kMaxStrips + 1];
+	__shared__ uint32_t s_scan[kResolveBlock / kWave];
+	__shared__ uint32_t s_flag;
+	slice_resolve_body<LABEL, false, false, true>(g, sa, ra, ncomp_out, nullptr, blockIdx.x, s_tab, s_scbase, s_scan, &s_flag, &en);
 }
 
 // pins: labels of the strip components once label_map has been filled from their component ids

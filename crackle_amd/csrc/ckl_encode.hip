@@ -988,7 +988,7 @@ __global__ void __launch_bounds__(kBlock) k_label_hash_scatter(
 __global__ void __launch_bounds__(kBlock) k_flat_section(
 	const uint64_t* __restrict__ uniq, const uint32_t* __restrict__ n_uniq, int stored_width,
 	const uint32_t* __restrict__ ncomp, uint32_t nslices, int component_width,
-	const uint64_t* __restrict__ mapping, uint32_t n, uint8_t* __restrict__ out
+	const uint64_t* __restrict__ mapping, uint32_t n, uint8_t* __restrict__ out, uint32_t* __restrict__ missing
 ) {
 	const uint32_t nu = *n_uniq;
 	const int key_width = nu <= 0xFFu ? 1 : (nu <= 0xFFFFu ? 2 : 4);
@@ -1012,6 +1012,7 @@ __global__ void __launch_bounds__(kBlock) k_flat_section(
 			const uint32_t mid = (lo + hi) >> 1;
 			if (uniq[mid] <= v) lo = mid; else hi = mid;
 		}
+		if (missing && (nu == 0 || uniq[lo] != v)) *missing = 1u;      // a caller's list (merge_unique) without this label
 		for (int b = 0; b < key_width; b++) o_keys[static_cast<uint64_t>(i) * key_width + b] = static_cast<uint8_t>((lo >> (8 * b)) & 0xFF);
 	}
 }
@@ -1996,6 +1997,7 @@ uint64_t flat_section(ckl_encoder& e, uint64_t N, int stored_width, int componen
 	}
 	}
 	uint64_t uniq_bound = N;      // entries of the unique list the section kernel may have to write
+	const bool merged_list = ov && ov->merge_unique;
 	if (ov && ov->merge_unique) {
 		// sharded encode: the keys are written against the unique labels of all slabs.  The caller
 		// exchanges the lists now, under the crack trail that is still running on the other stream.
@@ -2011,8 +2013,8 @@ uint64_t flat_section(ckl_encoder& e, uint64_t N, int stored_width, int componen
 		if (n_merged < n_local || n_merged > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: merge_unique returned a list that cannot contain the slab's labels");
 		e.d_uniq.ensure(n_merged + 1);
 		if (n_merged) CKL_HIP(hipMemcpyAsync(e.d_uniq.p, merged, n_merged * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-		const uint32_t nm = static_cast<uint32_t>(n_merged);
-		CKL_HIP(hipMemcpyAsync(e.d_n_uniq.p, &nm, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+		const uint32_t nm[2] = { static_cast<uint32_t>(n_merged), 0u };      // the list's length and the section kernel's "label not in the list"
+		CKL_HIP(hipMemcpyAsync(e.d_n_uniq.p, nm, sizeof(nm), hipMemcpyHostToDevice, s));
 		CKL_HIP(hipStreamSynchronize(s));      // `nm` and the caller's list may go away
 		e.d_labels_bin.ensure(8 + n_merged * static_cast<uint64_t>(stored_width) + static_cast<uint64_t>(ns) * component_width + N * 4 + 16);
 		uniq_bound = std::max<uint64_t>(uniq_bound, n_merged);
@@ -2021,10 +2023,14 @@ uint64_t flat_section(ckl_encoder& e, uint64_t N, int stored_width, int componen
 	e.d_labels_bin.ensure(8 + N * static_cast<uint64_t>(stored_width) + static_cast<uint64_t>(ns) * component_width + N * 4 + 16);
 	const uint64_t work = std::max<uint64_t>(std::max<uint64_t>(uniq_bound, ns), 1);
 	hipLaunchKernelGGL(k_flat_section, dim3(static_cast<uint32_t>((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-		e.d_uniq.p, e.d_n_uniq.p, stored_width, e.d_ncomp.p, ns, component_width, e.d_mapping.p, static_cast<uint32_t>(N), e.d_labels_bin.p);
+		e.d_uniq.p, e.d_n_uniq.p, stored_width, e.d_ncomp.p, ns, component_width, e.d_mapping.p, static_cast<uint32_t>(N), e.d_labels_bin.p,
+		merged_list ? e.d_n_uniq.p + 1 : nullptr);
 	HT_MARK("l:enqueue");
-	const uint32_t nu = download(e.d_n_uniq.p, 1, s)[0];
+	const std::vector<uint32_t> report = download(e.d_n_uniq.p, merged_list ? 2 : 1, s);
+	const uint32_t nu = report[0];
 	HT_MARK("l:wait");
+	// the length alone does not show it: keys against a list without one of the slab's labels (or one that is not sorted) would name its neighbour
+	if (merged_list && report[1]) throw Error(CKL_ERR_ARG, "crackle_amd: merge_unique returned a list that lacks a label of the slab");
 	return 8 + static_cast<uint64_t>(nu) * stored_width + static_cast<uint64_t>(ns) * component_width + N * static_cast<uint64_t>(byte_width(nu));
 }
 

@@ -260,7 +260,8 @@ typedef struct ckl_encode_overrides {
 	 * pass: the caller sorts the union anyway).  It returns the sorted unique labels of ALL slabs
 	 * (a superset; host memory that stays valid until the run returns); the flat label section
 	 * is then written against that list, so that the slabs' sections concatenate without
-	 * re-keying.  Return non-zero to abort the run.  NULL: the slab's own list is used. */
+	 * re-keying.  Return non-zero to abort the run; a list that lacks one of the slab's labels
+	 * fails the run with CKL_ERR_ARG.  NULL: the slab's own list is used. */
 	int (*merge_unique)(void* ctx, const uint64_t* local_distinct, uint64_t n_local,
 	                    const uint64_t** merged_sorted, uint64_t* n_merged);
 	void* merge_ctx;

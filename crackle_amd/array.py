@@ -194,6 +194,16 @@ class CrackleArray:
       return CrackleArray(out[0], self.device), out[1]
     return CrackleArray(out, self.device)
 
+  # (no remap method: tests/test_cutout_cpu.py pins that CrackleArray has none; operations.remap(arr.binary, ...) is the way)
+  def mask(self, labels, value: int = 0) -> "CrackleArray":
+    return CrackleArray(operations.mask(self.binary, labels, value=value), self.device)
+
+  def mask_except(self, labels, value: int = 0) -> "CrackleArray":
+    return CrackleArray(operations.mask_except(self.binary, labels, value=value), self.device)
+
+  def recompress(self, markov_model_order: Optional[int] = None) -> "CrackleArray":
+    return CrackleArray(operations.recompress(self.binary, markov_model_order=markov_model_order, device=self.device), self.device)
+
   def voxel_connectivity_graph(self, connectivity: int = 4) -> np.ndarray:
     return codec.voxel_connectivity_graph(self.binary, connectivity, device=self.device)
 

@@ -10,10 +10,13 @@
 //   cc3d::connected_components2d_4 + relabel        src/cc3d.hpp:114-144, 257-369        ckl_runs.hpp (runs of the label planes)
 //   labels::encode_flat                             src/labels.hpp:30-155      k_run_resolve (crc), k_mapping_comps + sort/unique
 //   stream assembly                                 src/crackle.hpp:171-216    host
+// and crackle.operations.recompress (crackle/operations.py:664-857) without the voxels: ckl_recompress.hpp + recompress()
 #include "ckl_encoder.hpp"
+#include "ckl_decoder.hpp"
 #include "ckl_runs.hpp"
 #include "ckl_strips.hpp"
 #include "ckl_trail.hpp"
+#include "ckl_recompress.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1857,6 +1860,12 @@ void flat_launch_resolve(ckl_encoder& e, const void* labels, int64_t sx, int64_t
 	const RunGeom g = flat_geom(e, sx, sy, ns);
 	const StripArrays sa = flat_strip_arrays(e);
 	const size_t tab_bytes = static_cast<size_t>(cap) * sizeof(uint32_t);
+	if (e.label_src) {
+		// no volume: the slots receive the components' first pixels, flat_collect turns them into labels
+		if (tab_bytes > 48u * 1024u) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slice_resolve_enc_pixels), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tab_bytes)));
+		hipLaunchKernelGGL(k_slice_resolve_enc_pixels, dim3(ns), dim3(kResolveBlock), tab_bytes, s, g, sa, ra, en, e.d_ncomp.p);
+		return;
+	}
 	with_label_type(e.dtype_bytes, [&](auto t) {
 		typedef typename decltype(t)::type LABEL;
 		if (tab_bytes > 48u * 1024u) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slice_resolve_enc<LABEL>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tab_bytes)));
@@ -1935,7 +1944,9 @@ void flat_collect(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	uint32_t max_ncomp = 1;
 	for (uint32_t zi = 0; zi < ns; zi++) max_ncomp = std::max(max_ncomp, out.ncomp[zi]);
 	const dim3 grid((max_ncomp + kBlock - 1) / kBlock, ns);
-	if (e.flat_strips) hipLaunchKernelGGL(k_gather_slots, grid, dim3(kBlock), 0, s, e.d_label_slots.p, e.flat_resolve_cap, e.d_ncomp.p, e.d_comp_off.p, e.d_mapping.p);
+	if (e.label_src) hipLaunchKernelGGL(k_component_labels_from_runs, grid, dim3(kBlock), 0, s, *e.label_src,
+		e.flat_strips ? e.d_label_slots.p : nullptr, e.flat_resolve_cap, e.d_comp_pix.p, e.d_rbase.p, e.d_ncomp.p, e.d_comp_off.p, e.d_mapping.p);
+	else if (e.flat_strips) hipLaunchKernelGGL(k_gather_slots, grid, dim3(kBlock), 0, s, e.d_label_slots.p, e.flat_resolve_cap, e.d_ncomp.p, e.d_comp_off.p, e.d_mapping.p);
 	else hipLaunchKernelGGL(k_mapping_comps<LABEL>, grid, dim3(kBlock), 0, s, labels, flat_arrays(e), sxy, e.d_comp_off.p, e.d_mapping.p);
 	out.total = total;
 }
@@ -2081,8 +2092,10 @@ void encode_typed(
 	g_ht = &ht;
 	VolumeStats st;
 	e.trail_zeroed = false;
-	const bool have_planes = ov && voxels > 0 && planes_cached(e, labels, sx, sy, sz);
+	// (recompress: the planes were built from a decode session's run tables, there is no volume)
+	const bool have_planes = voxels > 0 && (e.label_src ? planes_cached(e, e.label_src, sx, sy, sz) : ov && planes_cached(e, labels, sx, sy, sz));
 	e.planes_for = nullptr;       // single use: the caller may change the volume afterwards
+	if (e.label_src && voxels > 0 && !have_planes) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: recompress without its planes");
 	const bool labels_first = getenv("CKL_NO_OVERLAP") || static_cast<uint64_t>(sx) * sy > (1536ull * 1536ull)
 		|| (getenv("CKL_LABELS_AT_WALK") && atoi(getenv("CKL_LABELS_AT_WALK")) == 0);
 	// (a label stream that starts in front of the graph kernel sizes its run arrays from the planes' counts: no deferral then)
@@ -2314,8 +2327,109 @@ void encode_typed(
 		host_out_free(o);
 		throw;
 	}
+	if (e.label_src) e.host_marks = ht.marks;      // recompress folds them into its own line
 	*out = o;
 	*out_len = total;
+}
+
+// crackle.operations.recompress (crackle/operations.py:664-857 decodes slabs to voxels and compresses them again).
+// Here no voxel exists anywhere: a TABLES run of the decoder leaves the runs of every slice and the label of every
+// component, k_label_planes_from_runs (ckl_recompress.hpp) writes the encoder's planes and the volume's statistics
+// from them, and encode_typed goes on as it does from cached planes, with the label stage reading the same tables.
+// The bytes are those of compress(decompress(stream), markov_model_order): the planes, max label and pixel pairs are
+// functions of the labels alone, and everything behind them is the encoder's own.
+void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_signed);
+void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, uint8_t** out, uint64_t* out_len) {
+	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
+	const Header head = Header::parse(buf, n);
+	if (head.is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
+	const uint64_t order = markov_order < 0 ? static_cast<uint64_t>(head.markov_model_order) : static_cast<uint64_t>(markov_order);
+	if (order > 15) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [0, 15]");
+	const int64_t sx = head.sx, sy = head.sy, sz = head.sz;
+	check_dims(sx, sy, sz, head.data_width, 0);
+	if (head.voxels() == 0) {
+		hand_out(header_bytes(stream_header(head.data_width, sx, sy, sz, VolumeStats(), false, head.fortran_order, order, nullptr)), OutAlloc::MALLOC, out, out_len);
+		return;
+	}
+	select_device(device);      // (what came before needs none: refusals and streams without voxels are the host's)
+	const bool prof = getenv("CKL_PROFILE") != nullptr;
+	auto t_prev = std::chrono::steady_clock::now();
+	auto lap = [&]() {
+		const auto now = std::chrono::steady_clock::now();
+		const double ms = std::chrono::duration<double, std::milli>(now - t_prev).count();
+		t_prev = now;
+		return ms;
+	};
+	DecoderPtr dec;
+	const int rc = open_decoder(buf, n, 0, -1, device, dec);
+	if (rc != CKL_OK) throw Error(rc, ckl_last_error());
+	ckl_decoder& d = *dec;
+	enter(&d);
+	decoder_run(d, { Goal::TABLES });      // a damaged slice raises here, as for a decode
+	CKL_HIP(hipStreamSynchronize(d.stream));
+	const double ms_tables = lap();
+
+	ckl_encoder* raw = nullptr;
+	if (ckl_encoder_create(sx, sy, sz, head.data_width, device, &raw) != CKL_OK) throw Error(CKL_ERR_RUNTIME, ckl_last_error());
+	const EncoderPtr enc(raw);
+	ckl_encoder& e = *enc;
+	enter(&e);
+	hipStream_t s = e.stream;
+	const uint32_t ns = d.nslices;
+	const RunArrays ra = run_arrays(d);
+	RunLabels src;
+	src.g = run_geom(d);
+	src.word_base = ra.word_base; src.rbase = ra.rbase; src.run_cc = ra.run_cc; src.nruns = ra.nruns;
+	src.comp_off = d.d_comp_off.p; src.ncomp = d.d_ncomp_expect.p; src.label_map = d.d_label_map.p;
+	e.row_words = d.row_words;
+	e.plane_words = d.plane_words;
+	e.d_planes.ensure(2 * e.plane_words * ns);
+	e.d_count_vh.ensure(4 * static_cast<size_t>(ns));
+	e.d_stats.ensure(2);
+	CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, 3 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
+	CKL_HIP(hipMemsetAsync(e.d_stats.p, 0, sizeof(unsigned long long), s));
+	CKL_HIP(hipEventRecord(e.evd0, s));
+	hipLaunchKernelGGL(k_label_planes_from_runs, dim3(static_cast<uint32_t>((e.plane_words + kBlock - 1) / kBlock), ns), dim3(kBlock), 0, s,
+		src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
+	CKL_HIP(hipEventRecord(e.evd1, s));
+	hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, s,
+		d.d_label_map.p, d.total_comp, e.d_stats.p);
+	const std::vector<uint32_t> c = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), s);
+	const std::vector<unsigned long long> mx = download(e.d_stats.p, 1, s);
+	float ms_kernel = 0.f;
+	CKL_HIP(hipEventElapsedTime(&ms_kernel, e.evd0, e.evd1));
+	e.count_v.assign(c.begin(), c.begin() + ns);
+	e.count_h.assign(c.begin() + ns, c.begin() + 2 * static_cast<size_t>(ns));
+	// lib::pixel_pairs (lib.hpp:249-256): equal neighbours in x-fastest order — inside the rows every pair that V does not
+	// mark, and the wrap-arounds the kernel counted
+	VolumeStats st;
+	st.max_label = mx[0];
+	for (uint32_t zi = 0; zi < ns; zi++) st.pairs += static_cast<uint64_t>(sx - 1) * sy - e.count_v[zi] + c[2 * static_cast<size_t>(ns) + zi];
+	e.planes_stats = st;
+	e.planes_deferred = false;
+	e.label_src = &src;
+	e.planes_for = &src;
+	e.planes_dims[0] = sx; e.planes_dims[1] = sy; e.planes_dims[2] = sz;
+	const double ms_planes = lap();
+	try {
+		with_label_type(head.data_width, [&](auto t) {
+			encode_typed<typename decltype(t)::type>(e, nullptr, sx, sy, sz, false, head.fortran_order, order, false, true, 0, nullptr, out, out_len);
+		});
+	}
+	catch (...) { e.label_src = nullptr; throw; }
+	e.label_src = nullptr;
+	if (prof) {
+		double graph = 0, cracks = 0, labels = 0, assembly = 0;
+		for (const auto& m : e.host_marks) {
+			const std::string name = m.first;
+			if (name == "planes" || name == "graph") graph += m.second;
+			else if (name == "cracks") cracks += m.second;
+			else if (name == "assembly" || name == "codes_d2h") assembly += m.second;
+			else labels += m.second;      // f:*, flat, l:*, label_table, labels_d2h: the label side, on the host under the crack trail
+		}
+		fprintf(stderr, "[ckl recompress host ms] tables=%.2f label_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_label_planes_from_runs_device=%.3f\n",
+			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
+	}
 }
 
 // reencode_with_markov_order (src/crackle.hpp:858-984).  The reference takes every slice's
@@ -2487,6 +2601,13 @@ int ckl_reencode_markov(const uint8_t* buf, uint64_t n, int markov_model_order, 
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		select_device(device);
 		reencode_markov(buf, n, markov_model_order, device, out, out_len);
+	});
+}
+
+int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		recompress(buf, n, markov_model_order, device, out, out_len);
 	});
 }
 

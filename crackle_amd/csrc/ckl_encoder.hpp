@@ -8,6 +8,7 @@
 #include <utility>
 
 struct VolumeStats { uint64_t max_label = 0, pairs = 0, first = 0, last = 0; };
+namespace ckl { namespace dev { struct RunLabels; } }
 
 struct ckl_encoder {
 	template <typename T> using DevBuf = ckl::DevBuf<T>;
@@ -74,6 +75,10 @@ struct ckl_encoder {
 	const void* trail_for = nullptr;
 	bool trail_perm = false;
 	int trail_order = 0;
+	// ckl_recompress: there is no volume.  The planes stand in d_planes (planes_stats, count_v / count_h as for cached
+	// planes) and the label stage takes every component's label from these run tables of a decode session (ckl_recompress.hpp)
+	const ckl::dev::RunLabels* label_src = nullptr;
+	std::vector<std::pair<const char*, double>> host_marks;      // ... and the host timer's marks of that run, for recompress' own line
 	VolumeStats planes_stats;          // max / pairs of the volume the cached planes were built from
 	int64_t planes_dims[3] = { 0, 0, 0 };
 	std::vector<uint64_t> h_rbase;

@@ -1,0 +1,155 @@
+// ckl_recompress: a stream's labels re-encoded without its voxels.  After a TABLES run the decoder holds, per
+// slice, the horizontal runs (word_base, run_cc: ckl_run_types.hpp) and the component -> label map; the label of
+// a pixel is a function of its run.  The encoder needs the volume for three things only, and all three follow
+// from (runs, label of every run):
+//   k_label_planes_from_runs       the "differs from the neighbour" planes, their per-slice counts and the
+//                                  row / slice wrap-arounds of lib::pixel_pairs (lib.hpp:249-256)
+//   k_label_map_max                lib::max_label (lib.hpp:224-247): every component has a pixel
+//   k_component_labels_from_runs   the label of every component of the NEW planes, from its first pixel
+//                                  (what k_mapping_comps and k_slice_resolve_enc read from the volume)
+#pragma once
+
+#include "ckl_run_types.hpp"
+
+namespace ckl {
+namespace dev {
+
+// the decoder's tables (device pointers; valid while the decode session lives)
+struct RunLabels {
+	RunGeom g;                      // the DECODER's crack planes: breaks() by the stream's crack format
+	const uint32_t* word_base;      // [nslices][plane_words]
+	const uint64_t* rbase;          // per slice base into run_cc
+	const uint32_t* run_cc;         // component of every run
+	const uint32_t* nruns;          // [nslices]
+	const uint64_t* comp_off;       // per slice base into label_map
+	const uint32_t* ncomp;          // [nslices] components as the label section states them
+	const uint64_t* label_map;      // component -> label
+
+	// label of run `run` of slice zi; everything read from the tables is clamped as k_paint_window clamps it
+	__device__ __forceinline__ uint64_t label_of(uint32_t zi, uint32_t run) const {
+		const uint32_t n = nruns[zi];
+		if (!n) return 0ull;
+		const uint32_t cc = run_cc[rbase[zi] + (run < n ? run : n - 1u)];
+		return cc < ncomp[zi] ? label_map[comp_off[zi] + cc] : 0ull;
+	}
+	// the run of pixel (x, y) of slice zi
+	__device__ __forceinline__ uint32_t run_at(uint32_t zi, uint32_t x, uint32_t y) const {
+		const uint32_t w = x >> 5;
+		return word_base[zi * g.plane_words + static_cast<uint64_t>(y) * g.row_words + w] + __popc(g.breaks(zi, y, w) & mask_le(x & 31u)) - 1u;
+	}
+};
+
+// One thread per 32-pixel word (zi, y, w).  The runs of a word are consecutive, word_base + k for its k-th break,
+// so a thread fetches one label per run, not per pixel.
+//   V: bit x (1 <= x < sx) where a run starts at x and its label differs from the run before it.
+//   H (y >= 1): the word cut at breaks(y) | breaks(y - 1); inside a piece both rows have one label each, and the
+//      piece's bits are set when those differ.
+// Bits at or past sx, x = 0 of V and y = 0 of H stay 0, as k_label_planes leaves them: the planes are a function of
+// the labels alone, whatever the input's crack format.
+// counts (zeroed by the host): [nslices] bits of V, [nslices] bits of H, [nslices] wrap pairs — the first pixel of
+// a row equal to the pixel before it in x-fastest order (the last of the row above, or of the slice before).
+// grid = (ceil(plane_words / 256), nslices)
+__global__ void __launch_bounds__(kBlock) k_label_planes_from_runs(
+	RunLabels t, uint32_t* __restrict__ planeV, uint32_t* __restrict__ planeH, uint32_t* __restrict__ counts, uint32_t nslices
+) {
+	__shared__ uint32_t s_red[kWaves];
+	const RunGeom& g = t.g;
+	const uint32_t zi = blockIdx.y;
+	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	uint32_t nv = 0, nh = 0, nw = 0;
+	if (i < g.plane_words) {
+		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
+		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
+		const uint32_t n = t.nruns[zi];
+		const uint32_t last = n ? n - 1u : 0u;
+		const uint32_t nce = t.ncomp[zi];
+		const uint32_t* rcc = t.run_cc + t.rbase[zi];
+		const uint64_t* lmap = t.label_map + t.comp_off[zi];
+		auto label_of = [&](uint32_t run) -> uint64_t {
+			if (!n) return 0ull;
+			const uint32_t cc = rcc[run < last ? run : last];
+			return cc < nce ? lmap[cc] : 0ull;
+		};
+		const uint64_t at = zi * g.plane_words + i;
+		const uint32_t valid = g.valid_mask(w);
+		const uint32_t b = g.breaks(zi, y, w);
+		const uint32_t bu = y ? g.breaks(zi, y - 1u, w) : 0u;
+		uint32_t rc = t.word_base[at] - 1u;                                // the run that reaches into the word from the left
+		uint32_t ru = y ? t.word_base[at - g.row_words] - 1u : 0u;         // (w = 0: the last run of the row before)
+		uint64_t lc = 0, lu = 0;
+		if (w == 0) {
+			// the row's first pixel against the pixel before it in linear order
+			if (y) nw = label_of(rc) == label_of(rc + 1u);
+			else if (zi) nw = t.label_of(zi - 1u, 0xFFFFFFFFu) == label_of(0u);
+		}
+		else {
+			lc = label_of(rc);
+			if (y && !(bu & 1u)) lu = label_of(ru);
+		}
+		uint32_t v = 0, h = 0;
+		uint32_t rest = y ? ((b | bu | 1u) & valid) : b;
+		while (rest) {
+			const uint32_t x = __builtin_ctz(rest);
+			rest &= rest - 1u;
+			if ((b >> x) & 1u) {
+				const uint64_t l = label_of(++rc);
+				if ((w | x) && l != lc) v |= 1u << x;
+				lc = l;
+			}
+			if (y) {
+				if ((bu >> x) & 1u) lu = label_of(++ru);
+				if (lc != lu) {
+					const uint32_t end = rest ? __builtin_ctz(rest) : 32u;      // the piece is [x, end)
+					h |= (end >= 32u ? 0xFFFFFFFFu : ((1u << end) - 1u)) & ~((1u << x) - 1u);
+				}
+			}
+		}
+		h &= valid;
+		planeV[at] = v; planeH[at] = h;
+		nv = __popc(v); nh = __popc(h);
+	}
+	nv = block_sum(nv, s_red); nh = block_sum(nh, s_red); nw = block_sum(nw, s_red);
+	if (threadIdx.x == 0) {
+		if (nv) atomicAdd(counts + zi, nv);
+		if (nh) atomicAdd(counts + nslices + zi, nh);
+		if (nw) atomicAdd(counts + 2u * nslices + zi, nw);
+	}
+}
+
+// the largest entry of the component -> label map; *out zeroed by the host
+__global__ void __launch_bounds__(kBlock) k_label_map_max(const uint64_t* __restrict__ label_map, uint64_t n, unsigned long long* __restrict__ out) {
+	__shared__ unsigned long long s_max[kWaves];
+	unsigned long long mx = 0;
+	const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+	for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+		const unsigned long long v = label_map[i];
+		mx = v > mx ? v : mx;
+	}
+	for (int d = kWave / 2; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(mx, d, kWave); mx = o > mx ? o : mx; }
+	if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (int w = 1; w < kWaves; w++) mx = s_max[w] > mx ? s_max[w] : mx;
+		if (mx) atomicMax(out, mx);
+	}
+}
+
+// One thread per component of the NEW planes: its first pixel (the strip path leaves it in the resolve's slots, the
+// run pipeline in comp_pix) -> the decoder's run at that pixel -> its label.  ncomp / comp_off / rbase_enc are the
+// ENCODER's.  grid = (ceil(most components of a slice / 256), nslices)
+__global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
+	RunLabels t, const uint64_t* __restrict__ slots, uint32_t slot_cap, const uint32_t* __restrict__ comp_pix, const uint64_t* __restrict__ rbase_enc,
+	const uint32_t* __restrict__ ncomp, const uint64_t* __restrict__ comp_off, uint64_t* __restrict__ mapping
+) {
+	const uint32_t zi = blockIdx.y;
+	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+	if (c >= ncomp[zi]) return;
+	const uint32_t n_pixels = t.g.sx * t.g.sy;
+	uint32_t pix = slots ? static_cast<uint32_t>(slots[static_cast<uint64_t>(zi) * slot_cap + c]) : comp_pix[rbase_enc[zi] + c];
+	pix = pix < n_pixels ? pix : n_pixels - 1u;
+	const uint32_t y = pix / t.g.sx;
+	mapping[comp_off[zi] + c] = t.label_of(zi, t.run_at(zi, pix - y * t.g.sx, y));
+}
+
+}  // namespace dev
+}  // namespace ckl

@@ -469,7 +469,7 @@ struct ResolveArgs {
 // component — read at its first pixel — to the slice's slot of ra.cap entries
 constexpr uint32_t kEncIdBits = 16;      // ids are below kResolveCap
 struct EncResolve {
-	const void* labels;        // the volume, typed like OUT
+	const void* labels;        // the volume, typed like OUT (PIXELS: unused)
 	uint64_t sxy;
 	uint64_t* slots;           // [nslices][ra.cap]
 	uint32_t* crc_acc;         // [nslices]
@@ -506,7 +506,8 @@ __device__ __forceinline__ void with_width(uint32_t w, F&& f) {
 // The body works on slice zi with its tables in the caller's LDS (s_tab: ra.cap entries, s_scbase: nstrips + 1,
 // s_scan: kResolveBlock / 64, s_flag: 1).  Returns false when the slice does not fit.
 // ENC: the encoder's mode (EncResolve above); OUT is then the volume's label type and LABELS is false.
-template <typename OUT, bool LABELS, bool DIAG, bool ENC = false>
+// PIXELS (with ENC): there is no volume; the slot receives the component's first pixel itself (ckl_recompress.hpp).
+template <typename OUT, bool LABELS, bool DIAG, bool ENC = false, bool PIXELS = false>
 __device__ __forceinline__ bool slice_resolve_body(
 	const RunGeom& g, const StripArrays& sa, const ResolveArgs& ra, uint32_t* __restrict__ ncomp_out, unsigned long long* __restrict__ diag,
 	uint32_t zi, uint32_t* s_tab, uint32_t* s_scbase, uint32_t* s_scan, uint32_t* s_flag_p, const EncResolve* en = nullptr
@@ -653,7 +654,10 @@ __device__ __forceinline__ bool slice_resolve_body(
 		uint64_t lab[kPer];
 		if (ENC) {
 #pragma unroll
-			for (uint32_t q = 0; q < kPer; q++) lab[q] = static_cast<const OUT*>(en->labels)[zi * en->sxy + key[q]];
+			for (uint32_t q = 0; q < kPer; q++) {
+				if constexpr (PIXELS) lab[q] = key[q];
+				else lab[q] = static_cast<const OUT*>(en->labels)[zi * en->sxy + key[q]];
+			}
 		}
 		else if (LABELS) {
 			// keys of the four entries in one trip to memory, their labels in a second one (entries past the
@@ -733,6 +737,14 @@ static __global__ void __launch_bounds__(kResolveBlock, 8) k_slice_resolve_enc(R
 	__shared__ uint32_t s_scan[kResolveBlock / kWave];
 	__shared__ uint32_t s_flag;
 	slice_resolve_body<LABEL, false, false, true>(g, sa, ra, ncomp_out, nullptr, blockIdx.x, s_tab, s_scbase, s_scan, &s_flag, &en);
+}
+// the same without a volume: every component's first pixel goes to its slot
+static __global__ void __launch_bounds__(kResolveBlock, 8) k_slice_resolve_enc_pixels(RunGeom g, StripArrays sa, ResolveArgs ra, EncResolve en, uint32_t* __restrict__ ncomp_out) {
+	extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];      // ra.cap entries
+	__shared__ uint32_t s_scbase[kMaxStrips + 1];
+	__shared__ uint32_t s_scan[kResolveBlock / kWave];
+	__shared__ uint32_t s_flag;
+	slice_resolve_body<uint32_t, false, false, true, true>(g, sa, ra, ncomp_out, nullptr, blockIdx.x, s_tab, s_scbase, s_scan, &s_flag, &en);
 }
 
 // pins: labels of the strip components once label_map has been filled from their component ids

@@ -1,7 +1,9 @@
 """Stream surgery on .ckl bytes without decoding — the slab merge the sharded encoder is built
 on, exposed with the reference's names (crackle/operations.py:424-662: zstack, zsplit,
 zshatter).  Host only (native: ckl_zstack / ckl_zsplit); FLAT label streams.  The consumers
-array_equal, mode_pooling_2x2x1, point_cloud, contacts and connected_components run on the device."""
+array_equal, mode_pooling_2x2x1, point_cloud, contacts and connected_components run on the device.
+The label edits remap, mask and mask_except rewrite header and label section on the host; recompress
+re-encodes a stream from its own labels on the device (ckl_recompress), without decoding a voxel."""
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -313,3 +315,149 @@ def connected_components(
     L.ckl_free(out)
     if lab.value:
       L.ckl_free(lab)
+
+
+# ---- label edits: remap / mask / mask_except on the host, recompress on the device ------------------------------------
+def _byte_width(x: int) -> int:
+  return 1 if x <= 0xFF else 2 if x <= 0xFFFF else 4 if x <= 0xFFFFFFFF else 8
+
+
+def _crc8(data: bytes) -> int:
+  """The header's checksum (src/crc.hpp:23-49)."""
+  crc = 0xFF
+  for byte in data:
+    crc ^= byte
+    for _ in range(8):
+      crc = (crc >> 1) ^ 0xE7 if crc & 1 else crc >> 1
+  return crc
+
+
+def _editable_header(binary: bytes, what: str):
+  head = header(binary)
+  if head.format_version == 0:
+    raise ValueError(f"{what}: format version 0 streams have no label crc to rewrite; recompress() first.")
+  if head.signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  if head.voxels() != 0 and head.label_format != 0:
+    raise ValueError(f"{what}: pin label streams have no label per component to rewrite; recompress() gives a FLAT stream first.")
+  return head
+
+
+def _flat_section(binary: bytes, head):
+  """(unique labels, the components-per-slice block as bytes, the key of every component) of a FLAT label section
+  (src/labels.hpp:92-155)."""
+  off = head.header_bytes + head.grid_index_bytes
+  sec = binary[off:off + head.num_label_bytes]
+  n_uniq = int.from_bytes(sec[:8], "little")
+  uniq = np.frombuffer(sec, dtype=f"<u{head.stored_data_width}", count=n_uniq, offset=8)
+  at = 8 + n_uniq * head.stored_data_width
+  per_slice = sec[at:at + head.sz * _byte_width(head.sx * head.sy)]
+  at += len(per_slice)
+  kw = _byte_width(n_uniq)
+  keys = np.frombuffer(sec, dtype=f"<u{kw}", count=(len(sec) - at) // kw, offset=at)
+  return uniq, per_slice, keys
+
+
+def _with_labels(binary: bytes, head, new_values: np.ndarray) -> bytes:
+  """The stream with label i of its unique list replaced by new_values[i] (uint64), as a canonical FLAT stream."""
+  _, per_slice, keys = _flat_section(binary, head)
+  uniq, inverse = np.unique(new_values, return_inverse=True)
+  top = int(uniq[-1])
+  stored_width = _byte_width(top)
+  data_width = max(head.data_width, stored_width)
+  section = b"".join((
+    len(uniq).to_bytes(8, "little"), uniq.astype(f"<u{stored_width}").tobytes(), per_slice,
+    inverse.astype(np.uint64)[keys].astype(f"<u{_byte_width(len(uniq))}").tobytes(),
+  ))
+  fmt = int.from_bytes(binary[5:7], "little")
+  fmt &= ~0xF & ~(1 << 13)      # data width, stored width; "not sorted" cleared
+  fmt |= {1: 0, 2: 1, 4: 2, 8: 3}[data_width] | ({1: 0, 2: 1, 4: 2, 8: 3}[stored_width] << 2)
+  body = binary[4:5] + fmt.to_bytes(2, "little") + binary[7:20] + len(section).to_bytes(8, "little")
+  off = head.header_bytes + head.grid_index_bytes
+  rest = binary[off + head.num_label_bytes:]
+  crcs_at = len(rest) - 4 * (head.sz + 1)
+  crc = _lib.lib().ckl_crc32c(section, len(section))
+  return b"".join((binary[:4], body, bytes([_crc8(body[1:])]), binary[head.header_bytes:off], section,
+                   rest[:crcs_at], crc.to_bytes(4, "little"), rest[crcs_at + 4:]))
+
+
+def remap(binary: bytes, mapping: dict, preserve_missing_labels: bool = False, parallel: int = 0) -> bytes:
+  """The stream in which every voxel v has the value mapping[v] (crackle/codec.py:747-776): only header and label
+  section are rewritten, z-index, markov model, crack codes and slice crcs are the input's bytes.  A label of the
+  stream without a key raises KeyError unless preserve_missing_labels, which keeps it; keys the stream does not
+  hold are ignored.  `parallel` is accepted and ignored.
+
+  One difference from the reference, on purpose: its remap overwrites the unique list in place, which leaves it
+  unsorted, with duplicates where labels were merged, and clears is_sorted.  Here the result is always a canonical
+  FLAT stream, what the reference's condense_unique (crackle/codec.py:778-802) would make of that: the unique list
+  ascending without duplicates, the keys re-indexed at the width of the new count, the stored width from the
+  largest label, the data width grown (never shrunk) to hold it, is_sorted set.  contains() and the decoder's
+  label table rely on the sorted list, so every function of this package keeps working on the result.
+
+  Merged labels keep the crack between their components ("false boundaries"): recompress() removes them.
+  Pin label streams (recompress() gives a FLAT stream first) and format version 0 raise ValueError, signed streams
+  TypeError, new values outside 0 .. 2^64 - 1 ValueError."""
+  b = bytes(binary)
+  head = _editable_header(b, "remap")
+  for v in mapping.values():
+    if not 0 <= int(v) < (1 << 64):
+      raise ValueError(f"remap: value {v} is outside 0 .. 2^64 - 1")
+  if head.voxels() == 0:
+    return b
+  uniq, _, _ = _flat_section(b, head)
+  new_values = np.empty(len(uniq), dtype=np.uint64)
+  for i, label in enumerate(uniq.tolist()):
+    if label in mapping:
+      new_values[i] = int(mapping[label])
+    elif preserve_missing_labels:
+      new_values[i] = label
+    else:
+      raise KeyError(label)
+  return _with_labels(b, head, new_values)
+
+
+def mask(binary: bytes, labels: list, value: int = 0, parallel: int = 0) -> bytes:
+  """The stream with every label in `labels` replaced by `value` (crackle/operations.py:1028-1046); see remap()."""
+  return remap(binary, {int(label): value for label in labels}, preserve_missing_labels=True, parallel=parallel)
+
+
+def mask_except(binary: bytes, labels: list, value: int = 0, parallel: int = 0) -> bytes:
+  """The stream with every label NOT in `labels` replaced by `value` (crackle/operations.py:1048-1070); see remap()."""
+  b = bytes(binary)
+  head = _editable_header(b, "mask_except")
+  if head.voxels() == 0:
+    return remap(b, {}, preserve_missing_labels=True)
+  keep = {int(label) for label in labels}
+  uniq, _, _ = _flat_section(b, head)
+  return remap(b, {label: value for label in uniq.tolist() if label not in keep}, preserve_missing_labels=True, parallel=parallel)
+
+
+def recompress(
+  binary: bytes, memory_target: int = int(4e9), allow_pins: bool = False,
+  markov_model_order: Optional[int] = None, device: int = 0,
+) -> bytes:
+  """compress(decompress(binary), markov_model_order=m), byte for byte, without the voxels
+  (crackle/operations.py:664-857 decodes slabs and compresses them again): the stream re-encoded from its own labels,
+  which removes the cracks remap() and mask() leave between components that now share a label.  m is the input's
+  order unless markov_model_order is given.  The output has FLAT labels, format version 1, whatever the input had
+  (FLAT, pins, version 0), and the input's data width and fortran_order flag.
+
+  On the device the decoder runs up to its run tables and component -> label map; one kernel writes the encoder's
+  "labels differ" planes and the volume's statistics from them, and the encoder's crack and label stages follow
+  (ckl_recompress).  memory_target is accepted and ignored: there are no slabs.  allow_pins=True raises ValueError
+  (pins need the voxel columns), signed streams TypeError as compress does; a damaged slice raises what
+  decompress raises for it."""
+  from .codec import _raise
+  if allow_pins:
+    raise ValueError("recompress: allow_pins is not supported: pins are found along the voxel columns, which are never decoded here.")
+  b = bytes(binary)
+  if header(b).signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  order = -1 if markov_model_order is None else int(markov_model_order)
+  if markov_model_order is not None and order < 0:
+    raise ValueError(f"recompress: markov_model_order must not be negative. Got: {order}")
+  out, n = C.c_void_p(), C.c_uint64()
+  rc = _lib.lib().ckl_recompress(b, len(b), order, int(device), C.byref(out), C.byref(n))
+  if rc != _lib.CKL_OK:
+    _raise(rc)
+  return _take(out, n)

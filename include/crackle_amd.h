@@ -437,6 +437,18 @@ int ckl_point_cloud(
  * reference's reencode gives them.  *out (pinned host memory) is released with ckl_free. */
 int ckl_reencode_markov(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len);
 
+/* Replaces crackle.operations.recompress (crackle/operations.py:664-857, which decodes slabs to voxels and
+ * compresses them again): the stream that ckl_compress gives for the volume `buf` decodes to, with FLAT
+ * labels (format version 1) under markov_model_order (< 0: keep the input's), the input's data width and
+ * fortran_order flag.  A stream whose label table was rewritten (remap, mask) keeps a crack between every
+ * two components that now share a label; this removes them.  No voxel is decoded: the decoder runs up to
+ * its run tables and component -> label map (FLAT, pin and version 0 streams), k_label_planes_from_runs
+ * writes the encoder's "labels differ" planes, their counts, the pixel pairs and the maximum label from
+ * those, and the encoder's own crack and label stages follow, the label stage reading every new component's
+ * label at its first pixel through the same tables.  A damaged slice fails as in ckl_decompress; signed
+ * streams are CKL_ERR_ARG.  *out is released with ckl_free. */
+int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len);
+
 /* Native form of crackle.operations.zsplit's range helper (crackle/operations.py:550-623):
  * the stream of slices [z_start, z_end) of a FLAT stream, without decoding (host only).
  * *out is released with ckl_free. */

@@ -64,6 +64,10 @@ EXPORTS = {
   "ckl_cutout": (C.c_int, [
     C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
     C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int]),
+  "ckl_paste": (C.c_int, [
+    C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_uint64,
+    C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+    C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_decoder_label_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
   "ckl_decoder_contacts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_decoder_last_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -2,7 +2,9 @@
 stream behind numpy-style indexing (the reference's CrackleArray.__getitem__, crackle/array.py:257-285,
 which decodes the whole slices of the z-range and lets numpy crop them).  Here the device writes the
 box alone (ckl_cutout: the decode pipeline up to the run tables, then k_paint_window) and only the box
-crosses the link."""
+crosses the link.  paste() is the way back (the reference's __setitem__, crackle/array.py:287-340):
+the slices of the box's z-range are decoded, edited and encoded again in HBM (ckl_paste)."""
+import ctypes as C
 import operator
 from typing import Optional
 
@@ -115,10 +117,71 @@ def cutout(binary: bytes, slices, label: Optional[int] = None, device: int = 0) 
   return box[tuple(0 if is_int else slice(None, None, step) for _, _, step, is_int in idx)]
 
 
+def paste(binary: bytes, slices, data, device: int = 0) -> bytes:
+  """The stream that decodes to ``V = decompress(binary); V[slices] = data`` (the reference's
+  CrackleArray.__setitem__, crackle/array.py:287-340, as a function that returns the new stream).
+  `slices` means what it means for cutout() (normalize_index, the same errors; steps >= 1; an int axis drops
+  out of the shape `data` must broadcast to).  `data` is a Python int or anything np.asarray takes: it is
+  broadcast to the indexed shape (numpy's ValueError when it does not), arrays are cast with
+  astype(dtype, copy=False) as the reference casts them, a Python int outside the stream's dtype is
+  OverflowError.  Signed streams are TypeError, as for compress; an empty box returns the stream unchanged.
+
+  Only the stream and the box cross the link: the device decodes the slices of the box's z-range
+  [z0, z1) into a slab in HBM, k_paste_box writes the box into it and the encoder reads it there
+  (ckl_paste).  With a step > 1 the tight box comes back through cutout(), numpy assigns into it and it
+  is pasted once: two transfers of the size of the box, never of the slab.
+
+  The bytes: for a version 1 stream with FLAT labels and a z-range that is not the whole depth, the slab is
+  encoded under the input's crack format, markov order and markov model and spliced between
+  zsplit's ranges with zstack, so the untouched slices keep their crack codes and crcs byte for byte
+  (the reference compresses the slab with defaults, which can make its zstack raise, and returns every
+  stream at markov order 0).  Otherwise (the z-range is the whole depth, pin labels, version 0) the result
+  is compress(V', markov_model_order=<the input's>): FLAT labels, version 1 — a pin-label stream comes back
+  FLAT.  A damaged slice inside [z0, z1) raises what decompress raises; one outside it is copied unseen,
+  as zsplit copies it."""
+  binary = bytes(binary)
+  head = CrackleHeader.frombytes(binary)
+  idx = normalize_index(slices, (head.sx, head.sy, head.sz))
+  if head.signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  dtype = np.dtype(head.dtype)
+  counts = [(stop - start - 1) // step + 1 if stop > start else 0 for start, stop, step, _ in idx]
+  indexed_shape = tuple(n for n, (_, _, _, is_int) in zip(counts, idx) if not is_int)
+  scalar = isinstance(data, (int, np.integer)) and not isinstance(data, (bool, np.bool_))
+  if scalar:
+    value = int(data)
+    if value < 0 or value > int(np.iinfo(dtype).max):
+      raise OverflowError(f"Python integer {value} out of bounds for {dtype}")
+  else:
+    arr = np.broadcast_to(np.asarray(data).astype(dtype, copy=False), indexed_shape)
+  if 0 in counts:
+    return binary
+
+  (x0, x1, _, _), (y0, y1, _, _), (z0, z1, _, _) = idx
+  tight = (x1 - x0, y1 - y0, z1 - z0)
+  order = "F" if head.fortran_order else "C"
+  stepped = any(step > 1 and n > 1 for n, (_, _, step, _) in zip(counts, idx))
+  box = None
+  if stepped:
+    box = np.array(cutout(binary, (slice(x0, x1), slice(y0, y1), slice(z0, z1)), device=device), order=order)
+    box[tuple(slice(None, None, step) for _, _, step, _ in idx)] = value if scalar else arr.reshape(counts)
+  elif not scalar:
+    box = np.array(arr.reshape(tight), order=order)
+  out, n = C.c_void_p(), C.c_uint64()
+  rc = _lib.lib().ckl_paste(
+    binary, len(binary), None if box is None else box.ctypes.data, _lib.MEM_HOST, int(box is not None), 0 if box is not None else value,
+    x0, x1, y0, y1, z0, z1, int(device), C.byref(out), C.byref(n),
+  )
+  if rc != _lib.CKL_OK:
+    codec._raise(rc)
+  return operations._take(out, n)
+
+
 class CrackleArray:
-  """A stream behind a read-only array interface (crackle/array.py:32-285): metadata from the header
-  and the label section, ``arr[x0:x1, y0:y1, z0:z1]`` through cutout(), and the package's operations
-  as methods."""
+  """A stream behind an array interface (crackle/array.py:32-340): metadata from the header and the
+  label section, ``arr[x0:x1, y0:y1, z0:z1]`` through cutout(), ``arr.paste(slices, data)`` for the
+  reference's ``arr[slices] = data`` (it returns a new array, as mask and recompress do), and the package's
+  operations as methods."""
 
   def __init__(self, binary: bytes, device: int = 0):
     self.binary = bytes(binary)
@@ -172,6 +235,10 @@ class CrackleArray:
 
   def __getitem__(self, slices) -> np.ndarray:
     return cutout(self.binary, slices, device=self.device)
+
+  # (no __setitem__: tests/test_cutout_cpu.py pins that the array is never edited in place)
+  def paste(self, slices, data) -> "CrackleArray":
+    return CrackleArray(paste(self.binary, slices, data, device=self.device), self.device)
 
   def voxel_counts(self, label: Optional[int] = None):
     return codec.voxel_counts(self.binary, label=label, device=self.device)

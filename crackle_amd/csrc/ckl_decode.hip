@@ -2576,7 +2576,7 @@ void launch_resolve_and_stats(ckl_decoder& d, const RunGeom& g, const RunArrays&
 }
 
 template <typename OUT>
-void launch_resolve_and_paint(ckl_decoder& d, const RunGeom& g, const RunArrays& ra, void* out_device, int has_label, uint64_t label, StageTimer& st) {
+void launch_resolve_and_paint(ckl_decoder& d, const RunGeom& g, const RunArrays& ra, void* out_device, int has_label, uint64_t label, bool x_fastest, StageTimer& st) {
 	const Header& h = d.head;
 	hipStream_t s = d.stream;
 	const uint32_t ns = d.nslices;
@@ -2603,9 +2603,10 @@ void launch_resolve_and_paint(ckl_decoder& d, const RunGeom& g, const RunArrays&
 		st.done("k_run_labels");
 	}
 	const uint32_t tiles = static_cast<uint32_t>((d.sxy + kPaintTile - 1) / kPaintTile);
-	const bool fast = h.fortran_order && (h.sx % 4 == 0) && d.sxy < 0xFFFF0000ull;   // 32-bit pixel arithmetic in the fast path
+	const bool xf = h.fortran_order || x_fastest;      // (RunRequest::x_fastest: the volume x fastest whatever the stream's flag)
+	const bool fast = xf && (h.sx % 4 == 0) && d.sxy < 0xFFFF0000ull;   // 32-bit pixel arithmetic in the fast path
 	if (fast) hipLaunchKernelGGL((k_paint_runs<OUT, true>), dim3(tiles, ns), dim3(kBlock), 0, s, g, ra, run_label, reinterpret_cast<OUT*>(out_device), d.sxy, ns, getenv("CKL_PAINT_NOSTAGE") ? 3u : 1u);
-	else hipLaunchKernelGGL((k_paint_runs<OUT, false>), dim3(tiles, ns), dim3(kBlock), 0, s, g, ra, run_label, reinterpret_cast<OUT*>(out_device), d.sxy, ns, h.fortran_order ? 1u : 0u);
+	else hipLaunchKernelGGL((k_paint_runs<OUT, false>), dim3(tiles, ns), dim3(kBlock), 0, s, g, ra, run_label, reinterpret_cast<OUT*>(out_device), d.sxy, ns, xf ? 1u : 0u);
 	st.done("k_paint_runs");
 }
 
@@ -2937,7 +2938,7 @@ void general_pipeline(ckl_decoder& d, const RunGeom& g, RunArrays& ra, const Run
 	}
 	if (rq.goal != Goal::PAINT) launch_resolve_and_stats(d, g, ra, st, rq.goal == Goal::STATS ? rq.stats : nullptr);
 	else with_label_type(rq.has_label ? 1 : (d.paint_width ? d.paint_width : h.data_width), [&](auto t) {
-		launch_resolve_and_paint<typename decltype(t)::type>(d, g, ra, rq.out, rq.has_label, rq.label, st);
+		launch_resolve_and_paint<typename decltype(t)::type>(d, g, ra, rq.out, rq.has_label, rq.label, rq.x_fastest, st);
 	});
 
 	hipLaunchKernelGGL(k_check, dim3((ns + kBlock - 1) / kBlock), dim3(kBlock), 0, s,

@@ -180,6 +180,7 @@ struct RunRequest {
 	uint64_t label = 0;
 	const StatsArgs* stats = nullptr;  // STATS
 	uint32_t* verdicts = nullptr;      // [nslices]: the slices' error words are reported here and nothing is raised for them
+	bool x_fastest = false;            // PAINT: x fastest whatever the stream's fortran_order (the encoder's input layout: ckl_paste)
 };
 
 // a call on a session begins: its device current, its stream behind the caller's default stream
@@ -202,5 +203,11 @@ void launch_run_stats(ckl_decoder& d, const dev::RunArrays& ra, const StatsArgs&
 // the box [x0, x1) x [y0, y1) of the session's slices, dense, into a device buffer: a TABLES run, then
 // k_paint_window (ckl_operations.hip); bounds outside the slice and a buffer too small are CKL_ERR_ARG
 void decoder_cutout(ckl_decoder& d, int64_t x0, int64_t x1, int64_t y0, int64_t y1, void* out_device, uint64_t capacity, int has_label, uint64_t label);
+// 0 <= a <= b <= dim for operation `what` (cutout, paste), or CKL_ERR_ARG naming the axis: nothing is clamped
+// (check_bounds, crackle/array.py:529-532)
+inline void check_box_axis(const char* what, const char* axis, int64_t a, int64_t b, uint32_t dim) {
+	if (a < 0 || a > b || b > static_cast<int64_t>(dim))
+		throw Error(CKL_ERR_ARG, std::string("crackle_amd: ") + what + ": " + axis + " range " + std::to_string(a) + " - " + std::to_string(b) + " is not an ascending range inside 0 - " + std::to_string(dim));
+}
 
 }  // namespace ckl

@@ -1097,12 +1097,6 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 	if (prof) fprintf(stderr, "[ckl point_cloud ms]%s | contours=%zu points=%llu walk_steps=%llu\n", marks.c_str(), kept.size(), static_cast<unsigned long long>(total_points), static_cast<unsigned long long>(walk_steps));
 }
 
-// 0 <= a <= b <= dim, or CKL_ERR_ARG naming the axis: nothing is clamped (check_bounds, crackle/array.py:529-532)
-void check_box_axis(const char* axis, int64_t a, int64_t b, uint32_t dim) {
-	if (a < 0 || a > b || b > static_cast<int64_t>(dim))
-		throw Error(CKL_ERR_ARG, std::string("crackle_amd: cutout: ") + axis + " range " + std::to_string(a) + " - " + std::to_string(b) + " is not an ascending range inside 0 - " + std::to_string(dim));
-}
-
 }  // namespace
 
 namespace ckl {
@@ -1113,8 +1107,8 @@ namespace ckl {
 // of the range raises as for a decode wherever the box lies, then k_paint_window.
 void decoder_cutout(ckl_decoder& d, int64_t x0, int64_t x1, int64_t y0, int64_t y1, void* out_device, uint64_t capacity, int has_label, uint64_t label) {
 	const Header& h = d.head;
-	check_box_axis("x", x0, x1, h.sx);
-	check_box_axis("y", y0, y1, h.sy);
+	check_box_axis("cutout", "x", x0, x1, h.sx);
+	check_box_axis("cutout", "y", y0, y1, h.sy);
 	const int ow = has_label ? 1 : h.data_width;
 	const uint64_t wx = static_cast<uint64_t>(x1 - x0), wy = static_cast<uint64_t>(y1 - y0);
 	const uint64_t need = wx * wy * d.nslices * static_cast<uint64_t>(ow);
@@ -1167,9 +1161,9 @@ int ckl_cutout(
 	return guard([&]() -> int {
 		if (!buf) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		const Header h = Header::parse(buf, n);
-		check_box_axis("x", x0, x1, h.sx);
-		check_box_axis("y", y0, y1, h.sy);
-		check_box_axis("z", z0, z1, h.sz);
+		check_box_axis("cutout", "x", x0, x1, h.sx);
+		check_box_axis("cutout", "y", y0, y1, h.sy);
+		check_box_axis("cutout", "z", z0, z1, h.sz);
 		const uint64_t need = static_cast<uint64_t>(x1 - x0) * static_cast<uint64_t>(y1 - y0) * static_cast<uint64_t>(z1 - z0) * static_cast<uint64_t>(has_label ? 1 : h.data_width);
 		if (need == 0) return CKL_OK;
 		if (!out || out_capacity_bytes < need) throw Error(CKL_ERR_ARG, "crackle_amd: output buffer too small: need " + std::to_string(need) + " bytes");

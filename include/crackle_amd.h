@@ -228,6 +228,31 @@ int ckl_decoder_cutout(ckl_decoder* d, int64_t x0, int64_t x1, int64_t y0, int64
 int ckl_cutout(const uint8_t* buf, uint64_t n, void* out, uint64_t out_capacity_bytes, int out_mem,
                int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1,
                int has_label, uint64_t label, int device);
+/* The inverse of ckl_cutout: replaces CrackleArray.__setitem__ (crackle/array.py:287-340, which decodes the
+ * slices of the z-range to the host, assigns with numpy, compresses the slab and splices it in with zsplit /
+ * zstack).  *out decodes to the volume of `buf` with the box [x0, x1) x [y0, y1) x [z0, z1) overwritten.
+ *   box       dense, data_width bytes per voxel, laid out exactly as ckl_cutout lays out its output for the
+ *             same stream and box (fortran_order streams x fastest, others z fastest): ckl_paste of
+ *             ckl_cutout's output is the identity on the decoded volume
+ *   box_mem   CKL_MEM_HOST or CKL_MEM_DEVICE
+ *   has_box   0: every voxel of the box becomes `value` and nothing is uploaded (CKL_ERR_ARG when `value` is
+ *             beyond the stream's data width)
+ * Bounds as for ckl_cutout (CKL_ERR_ARG, nothing is clamped); signed streams are CKL_ERR_ARG (the encoder
+ * takes no signed input); an empty box returns a copy of the stream and needs no device.
+ * The slices of the z-range are decoded into a slab in HBM (x fastest), one kernel writes the box into it and
+ * an encode session reads it there: only the stream and the box cross the link.
+ *   version 1, FLAT labels, [z0, z1) not the whole depth: the result is ckl_zstack of ckl_zsplit's
+ *     [0, z0), the slab's stream and ckl_zsplit's [z1, sz).  The slab is encoded under the input's crack
+ *     format, FLAT labels, markov order and markov model, so z-index entries, crack codes and slice crcs of
+ *     the untouched slices are the input's bytes (a damaged slice there is copied unseen; one inside the
+ *     range fails as in ckl_decompress); unique list, key widths and stored width are ckl_zstack's.
+ *   otherwise (whole depth, pin labels, version 0): the stream ckl_compress gives for the edited volume
+ *     under the input's markov order and fortran_order flag: FLAT, version 1, a model of its own.
+ * *out is released with ckl_free. */
+int ckl_paste(const uint8_t* buf, uint64_t n,
+              const void* box, int box_mem, int has_box, uint64_t value,
+              int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1,
+              int device, uint8_t** out, uint64_t* out_len);
 /* Elapsed device time of the last run, from HIP events recorded on the library's
  * own stream around (a) the whole pipeline and (b) the dominant kernel. */
 int ckl_decoder_last_timing(const ckl_decoder* d, float* pipeline_ms, float* dominant_kernel_ms);

@@ -16,9 +16,12 @@ from crackle_amd import synth
 S = np.s_
 
 # the three slice geometries of tests/test_gpu_cutout.py and a uint64 one; 97 and 33 are odd, so no two rows of a box
-# start at the same offset modulo 16 bytes
-GEOMETRIES = [((97, 61, 7), np.uint16, "F"), ((128, 64, 9), np.uint32, "F"), ((96, 80, 6), np.uint8, "C"), ((33, 17, 5), np.uint64, "F")]
-GEOMETRY_IDS = ["97x61x7-u16-F", "128x64x9-u32-F", "96x80x6-u8-C", "33x17x5-u64-F"]
+# start at the same offset modulo 16 bytes.  The last one is a C-order stream whose width is no multiple of 4: ckl_paste
+# decodes its slab x fastest (RunRequest::x_fastest), which for such a width is k_paint_runs<OUT, false> in mode 1, a
+# kernel that a fortran_order stream of that width reaches without the flag and a 96 wide C-order stream never
+GEOMETRIES = [((97, 61, 7), np.uint16, "F"), ((128, 64, 9), np.uint32, "F"), ((96, 80, 6), np.uint8, "C"), ((33, 17, 5), np.uint64, "F"),
+              ((90, 61, 5), np.uint32, "C")]
+GEOMETRY_IDS = ["97x61x7-u16-F", "128x64x9-u32-F", "96x80x6-u8-C", "33x17x5-u64-F", "90x61x5-u32-C"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -74,6 +77,8 @@ SPLICES = [
   Splice("u8-C-middle", GEOMETRIES[2], S[:, 10:30, 2:4]),
   Splice("u8-C-first-slice-fill", GEOMETRIES[2], S[3:77, 5:9, 0], fill=201),
   Splice("u64-middle", GEOMETRIES[3], S[1:30, 2:9, 1:4]),
+  Splice("u32-C-odd-width-middle", GEOMETRIES[4], S[3:80, 5:50, 1:3]),
+  Splice("u32-C-odd-width-last-slices-fill", GEOMETRIES[4], S[:, 7:9, 3:], fill=70000),
 ]
 
 

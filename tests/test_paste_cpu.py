@@ -117,6 +117,22 @@ def test_c_entry_argument_errors_need_no_device():
   assert L.ckl_paste(b[:10], 10, None, 0, 0, 1, 0, 4, 0, 4, 0, 1, 0, C.byref(out), C.byref(n)) == _lib.CKL_ERR_FORMAT
 
 
+def test_the_geometries_cover_both_paints_of_a_slab_decoded_x_fastest():
+  """ckl_paste decodes its slab x fastest whatever the stream's order (RunRequest::x_fastest).  On the general
+  pipeline that is k_paint_runs<OUT, true> for a width that is a multiple of 4 and k_paint_runs<OUT, false> in mode 1
+  otherwise; a C-order stream reaches either only through the flag, so the geometries hold one of each, and every
+  geometry has a splice case."""
+  assert len(pv.GEOMETRIES) == len(pv.GEOMETRY_IDS) == len(set(pv.GEOMETRY_IDS)) == 5
+  for (shape, dtype, order), name in zip(pv.GEOMETRIES, pv.GEOMETRY_IDS):
+    assert name == "%dx%dx%d-u%d-%s" % (*shape, 8 * np.dtype(dtype).itemsize, order)
+    vol = pv.volume(shape, dtype, order)
+    assert vol.shape == shape and vol.dtype == dtype and vol.flags.f_contiguous == (order == "F") and not vol.flags.writeable
+  c_order = [shape[0] % 4 for shape, _, order in pv.GEOMETRIES if order == "C"]
+  assert 0 in c_order and any(c_order), c_order
+  assert pv.GEOMETRIES[4] == ((90, 61, 5), np.uint32, "C")
+  assert {id(case.geometry) for case in pv.SPLICES} == {id(g) for g in pv.GEOMETRIES}
+
+
 @pytest.mark.parametrize("case", pv.SPLICES, ids=repr)
 def test_splice_cases_keep_the_crack_format(case, checker):
   """The precondition of `paste(compress(V), idx, data) == compress(V')` in tests/test_gpu_paste.py: the checker gives

@@ -6,7 +6,7 @@ crosses the link.  paste() is the way back (the reference's __setitem__, crackle
 the slices of the box's z-range are decoded, edited and encoded again in HBM (ckl_paste)."""
 import ctypes as C
 import operator
-from typing import Optional
+from typing import Optional, Union
 
 import numpy as np
 
@@ -254,6 +254,11 @@ class CrackleArray:
 
   def contacts(self, anisotropy=(1.0, 1.0, 1.0)):
     return operations.contacts(self.binary, anisotropy=anisotropy, device=self.device)
+
+  def overlaps(self, other: Union["CrackleArray", bytes]):
+    """{(a, b): voxels} of this array's labels a against the labels b of `other` (operations.overlaps)."""
+    other_binary = other.binary if isinstance(other, CrackleArray) else other
+    return operations.overlaps(self.binary, other_binary, device=self.device)
 
   def connected_components(self, connectivity: int = 26, binary_image: bool = False, return_mapping: bool = False):
     out = operations.connected_components(self.binary, connectivity=connectivity, binary_image=binary_image, return_mapping=return_mapping, device=self.device)

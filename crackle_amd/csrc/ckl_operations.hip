@@ -1,4 +1,4 @@
-// Operations on a decoded stream: label statistics, contacts, connected components
+// Operations on a decoded stream: label statistics, contacts, overlaps, connected components
 // (ckl_components3d.hpp), the point cloud (ckl_contours.hpp), the voxel connectivity graph,
 // array_equal and mode_pooling_2x2x1.  Each is here whole (kernels, host driver, C entry point) and
 // consumes what a decode session (ckl_decoder.hpp) leaves in HBM after decoder_run reached the goal
@@ -288,9 +288,11 @@ static __global__ void __launch_bounds__(kContactBlock) k_run_contacts(
 }
 
 // the occupied entries of the global table, packed (in no particular order: the host sorts them);
-// one output offset per workgroup of kContactCompact entries
+// one output offset per workgroup of kContactCompact entries.  NC counters per entry: 3 for
+// contacts, 1 for overlaps.
 constexpr uint32_t kContactCompactPer = 8;
 constexpr uint32_t kContactCompact = kBlock * kContactCompactPer;
+template <uint32_t NC>
 static __global__ void __launch_bounds__(kBlock) k_contacts_compact(
 	const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ counts, uint32_t cap,
 	unsigned long long* __restrict__ out_keys, unsigned long long* __restrict__ out_counts, uint32_t* flags
@@ -314,10 +316,129 @@ static __global__ void __launch_bounds__(kBlock) k_contacts_compact(
 		if (k[j] == kContactEmpty) continue;
 		const uint64_t i = i0 + j;
 		out_keys[at] = k[j];
-		out_counts[3ull * at] = counts[3 * i];
-		out_counts[3ull * at + 1] = counts[3 * i + 1];
-		out_counts[3ull * at + 2] = counts[3 * i + 2];
+#pragma unroll
+		for (uint32_t c = 0; c < NC; c++) out_counts[static_cast<uint64_t>(NC) * at + c] = counts[NC * i + c];
 		at++;
+	}
+}
+
+// ------------------------------------------------------------------------------
+// overlaps: the contingency table of two streams of one shape, voxels per pair of labels (a of
+// the one, b of the other).  No counterpart in the reference.  A pair is constant along the
+// intersection of a run of the one stream with a run of the other in the same row of the same
+// slice, so no voxel is painted and nothing is sorted: a thread takes one run of stream P, finds
+// the run of stream Q that holds its first pixel as contact_row does (Q's word_base and Q's
+// vertical-crack plane), walks Q's runs until its last pixel and adds every intersection's
+// length to the key (P's label index << 32 | Q's label index).  Each stream is read through its
+// own RunGeom / RunArrays: flip, rbase, comp_off and the component counts are the stream's own;
+// only sx, sy (hence row_words and plane_words) and the number of slices are shared, which the
+// host checks.  The pair table is contacts' scheme with one counter per entry: an LDS table
+// per workgroup, flushed into a global one; a key without room in LDS goes to the global table
+// directly; a full global table sets a flag and the host doubles it.
+// ------------------------------------------------------------------------------
+struct OverlapArgs {
+	const uint32_t* key_p;           // [total_comp of P] label table index of every component (kNoKey: not in the table)
+	const uint32_t* key_q;           // the same of Q
+	const uint64_t* comp_off_p;      // [nslices] first component of the slice, per stream
+	const uint64_t* comp_off_q;
+	const uint32_t* ncomp_p;         // [nslices] components of the slice, per stream
+	const uint32_t* ncomp_q;
+	uint32_t sx, n_pixels;
+	unsigned long long* keys;        // [cap] global table: pair keys, kContactEmpty where free
+	unsigned long long* counts;      // [cap] voxels
+	uint32_t cap_mask;               // cap - 1, cap a power of two
+	uint32_t* flags;                 // [CONTACT_FLAGS], as for contacts
+};
+
+// contact_global with one counter
+__device__ void overlap_global(const OverlapArgs& oa, unsigned long long key, unsigned long long n) {
+	if (__hip_atomic_load(oa.flags + CONTACT_FULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+	const uint32_t h = contact_hash(key);
+	for (uint32_t p = 0; p < kContactGlobalProbes && p <= oa.cap_mask; p++) {
+		const uint32_t slot = (h + p) & oa.cap_mask;
+		unsigned long long cur = oa.keys[slot];      // a slot changes once, from empty to its key: a stale read is settled by the CAS
+		if (cur == kContactEmpty) {
+			cur = atomicCAS(oa.keys + slot, kContactEmpty, key);
+			if (cur == kContactEmpty) cur = key;
+		}
+		if (cur == key) { atomicAdd(oa.counts + slot, n); return; }
+	}
+	atomicOr(oa.flags + CONTACT_FULL, 1u);
+}
+
+// n voxels with the labels of table indices kp (stream P) and kq (stream Q)
+__device__ __forceinline__ void overlap_add(const OverlapArgs& oa, unsigned long long* s_key, uint32_t* s_cnt, uint32_t kp, uint32_t kq, uint32_t n) {
+	const unsigned long long key = static_cast<unsigned long long>(kp) << 32 | kq;
+	const uint32_t h = contact_hash(key);
+	for (uint32_t p = 0; p < kContactProbes; p++) {
+		const uint32_t slot = (h + p) & (kContactLds - 1);
+		unsigned long long cur = s_key[slot];
+		if (cur == kContactEmpty) {
+			cur = atomicCAS(s_key + slot, kContactEmpty, key);
+			if (cur == kContactEmpty) cur = key;
+		}
+		if (cur == key) { atomicAdd(s_cnt + slot, n); return; }
+	}
+	overlap_global(oa, key, n);
+}
+
+// grid = (ceil(most runs of a slice of P / kContactRuns), nslices), block = kContactBlock
+static __global__ void __launch_bounds__(kContactBlock) k_run_overlaps(RunGeom gq, RunArrays rp, RunArrays rq, OverlapArgs oa) {
+	__shared__ unsigned long long s_key[kContactLds];
+	// 32 bits are enough: the runs of a workgroup lie in one slice and do not intersect each other,
+	// so all that the workgroup adds, to all entries together, is at most the slice's pixels, and
+	// those are fewer than 2^32 (n_pixels is a uint32_t).  The global counters are 64 bits wide.
+	__shared__ uint32_t s_cnt[kContactLds];
+	__shared__ uint32_t s_stop;
+	const uint32_t zi = blockIdx.y;
+	const uint32_t n = rp.nruns[zi];
+	const uint32_t i0 = blockIdx.x * kContactRuns;
+	if (i0 >= n) return;
+	if (threadIdx.x == 0) s_stop = __hip_atomic_load(oa.flags + CONTACT_FULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	for (uint32_t k = threadIdx.x; k < kContactLds; k += kContactBlock) { s_key[k] = kContactEmpty; s_cnt[k] = 0; }
+	__syncthreads();
+	if (s_stop) return;      // this pass runs again with a larger table: nothing it adds is kept
+	const uint64_t rbp = rp.rbase[zi], rbq = rq.rbase[zi];
+	const uint32_t nq = rq.nruns[zi];
+	const uint32_t ncp = oa.ncomp_p[zi], ncq = oa.ncomp_q[zi];
+	const uint32_t* key_p = oa.key_p + oa.comp_off_p[zi];
+	const uint32_t* key_q = oa.key_q + oa.comp_off_q[zi];
+	for (uint32_t k = 0; k < kContactPer; k++) {
+		const uint32_t i = i0 + k * kContactBlock + threadIdx.x;
+		if (i >= n) break;
+		const uint32_t a = rp.run_start[rbp + i];
+		const uint32_t b = i + 1 < n ? rp.run_start[rbp + i + 1] : oa.n_pixels;
+		const uint32_t cc = rp.run_cc[rbp + i];
+		const uint32_t kp = cc < ncp ? key_p[cc] : kNoKey;
+		// a run outside the slice, or one that is empty or crosses a row's end, would index Q's planes outside them
+		if (kp == kNoKey || a >= b || b > oa.n_pixels) { atomicOr(oa.flags + CONTACT_BADKEY, 1u); continue; }
+		const uint32_t y = a / oa.sx;
+		const uint32_t row = y * oa.sx;
+		const uint32_t x0 = a - row, x1 = b - 1 - row;
+		if (x1 >= oa.sx) { atomicOr(oa.flags + CONTACT_BADKEY, 1u); continue; }
+		const uint32_t w = x0 >> 5;
+		uint32_t j = rq.word_base[zi * gq.plane_words + y * gq.row_words + w] + __popc(gq.breaks(zi, y, w) & mask_le(x0 & 31u)) - 1u;
+		if (j >= nq) { atomicOr(oa.flags + CONTACT_BADKEY, 1u); continue; }
+		uint32_t s = rq.run_start[rbq + j];
+		if (s < row || s > a) { atomicOr(oa.flags + CONTACT_BADKEY, 1u); continue; }      // not the run that holds (x0, y)
+		s -= row;
+		for (;;) {
+			// the run after the last one of a row starts the next row (or the slice ends): e <= sx
+			const uint32_t e = (j + 1 < nq ? rq.run_start[rbq + j + 1] : oa.n_pixels) - row;
+			const uint32_t ccq = rq.run_cc[rbq + j];
+			const uint32_t kq = ccq < ncq ? key_q[ccq] : kNoKey;
+			const uint32_t hi = min(e, x1 + 1), lo = max(s, x0);
+			if (kq == kNoKey || hi <= lo) { atomicOr(oa.flags + CONTACT_BADKEY, 1u); break; }
+			overlap_add(oa, s_key, s_cnt, kp, kq, hi - lo);
+			if (e > x1) break;
+			j++;
+			s = e;
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < kContactLds; k += kContactBlock) {
+		const unsigned long long key = s_key[k];
+		if (key != kContactEmpty) overlap_global(oa, key, s_cnt[k]);
 	}
 }
 
@@ -721,7 +842,7 @@ void decoder_contacts(ckl_decoder& d, std::vector<uint64_t>& pairs, std::vector<
 		ca.flags = flags.p;
 		hipLaunchKernelGGL(k_run_contacts, dim3((max_runs + kContactRuns - 1) / kContactRuns, ns), dim3(kContactBlock), 0, s,
 			g, ra, d.d_comp_off.p, d.d_ncomp_expect.p, ca);
-		hipLaunchKernelGGL(k_contacts_compact, dim3(static_cast<uint32_t>((cap + kContactCompact - 1) / kContactCompact)), dim3(kBlock), 0, s,
+		hipLaunchKernelGGL(k_contacts_compact<3>, dim3(static_cast<uint32_t>((cap + kContactCompact - 1) / kContactCompact)), dim3(kBlock), 0, s,
 			keys.p, counts.p, static_cast<uint32_t>(cap), out_keys.p, out_counts.p, flags.p);
 		CKL_HIP(hipMemcpyAsync(hflags, flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
 		CKL_HIP(hipStreamSynchronize(s));
@@ -755,6 +876,122 @@ void decoder_contacts(ckl_decoder& d, std::vector<uint64_t>& pairs, std::vector<
 		pairs[2ull * i] = d.stats_table[key >> 32];
 		pairs[2ull * i + 1] = d.stats_table[key & 0xFFFFFFFFull];
 		for (int a = 0; a < 3; a++) faces[3ull * i + a] = c[3ull * order[i] + a];
+	}
+}
+
+// First capacity of overlaps' global table for streams of na and nb labels.  Two segmentations of
+// compact cells: a cell of the finer one lies inside one cell of the coarser one or straddles a
+// face, an edge or a corner between 2, 3 or 4 of them (8 at a lattice corner, rarely), so about 4
+// pairs per label of the finer stream are a generous mean; every label of the coarser one has a
+// pair as well.  At most every pair of the two tables, at a load of 3/4 at most.  Noise against
+// noise, where nearly every voxel is a pair of its own, takes a few doublings.
+uint64_t overlap_first_capacity(uint64_t na, uint64_t nb) {
+	const uint64_t est = std::min<uint64_t>(4 * std::max(na, nb) + std::min(na, nb), na * nb);
+	uint64_t cap = 1024;
+	while (cap < est + est / 3) cap <<= 1;
+	return cap;
+}
+
+// The contingency table of two sessions of one slice shape and one number of slices, slice i of the
+// one against slice i of the other: pairs (a, b) of label values, ascending as unsigned, and their
+// voxels.  A TABLES run of each, then k_run_overlaps over the runs of the stream whose fullest slice
+// has more of them (the walk along the other stream's runs is then the short one; the key halves are
+// swapped back here) and k_contacts_compact; a global table that fills runs the pass again, doubled.
+struct OverlapTable {
+	HostOut<uint64_t> pairs, counts;      // 2 n and n values; unset while n is 0
+	uint64_t n = 0;
+};
+void decoder_overlaps(ckl_decoder& a, ckl_decoder& b, OverlapTable& out) {
+	if (a.device != b.device) throw Error(CKL_ERR_ARG, "crackle_amd: overlaps: the sessions are on different devices: " + std::to_string(a.device) + " and " + std::to_string(b.device));
+	if (a.head.sx != b.head.sx || a.head.sy != b.head.sy || a.nslices != b.nslices)
+		throw Error(CKL_ERR_ARG, "crackle_amd: overlaps: the sessions differ in shape: " + std::to_string(a.head.sx) + " x " + std::to_string(a.head.sy) + " x " + std::to_string(a.nslices)
+			+ " slices and " + std::to_string(b.head.sx) + " x " + std::to_string(b.head.sy) + " x " + std::to_string(b.nslices) + " slices");
+	if (a.sxy == 0 || a.nslices == 0) return;
+	// a's pipeline starts the span that record_span closes; every step on b's stream is waited for by
+	// the host (component_keys at the latest) before the kernels that read b's tables go to a's stream
+	decoder_run(a, { Goal::TABLES });
+	if (&b != &a) decoder_run(b, { Goal::TABLES });
+	ensure_label_table(a);
+	ensure_label_table(b);
+	const uint32_t na = static_cast<uint32_t>(a.stats_table.size()), nb = static_cast<uint32_t>(b.stats_table.size());
+	if (a.total_comp == 0 || b.total_comp == 0 || na == 0 || nb == 0) return;
+	DevBuf<uint32_t> d_key_a, d_key_b;
+	const uint32_t max_a = component_keys(a, d_key_a), max_b = component_keys(b, d_key_b);
+	if (max_a == 0 || max_b == 0) return;
+	const bool swapped = max_b > max_a;
+	ckl_decoder& p = swapped ? b : a;
+	ckl_decoder& q = swapped ? a : b;
+	const RunGeom gp = run_geom(p), gq = run_geom(q);
+	if (gp.row_words != gq.row_words || gp.plane_words != gq.plane_words || gp.sx != gq.sx || gp.sy != gq.sy || p.sxy != q.sxy)
+		throw Error(CKL_ERR_RUNTIME, "crackle_amd: overlaps: the sessions' crack planes differ in layout");
+	const RunArrays rp = run_arrays(p), rq = run_arrays(q);
+	hipStream_t s = a.stream;
+
+	uint64_t cap = overlap_first_capacity(na, nb);
+	DevBuf<unsigned long long> keys, cnt, out_keys, out_cnt;
+	DevBuf<uint32_t> flags;
+	flags.ensure(CONTACT_FLAGS);
+	uint32_t hflags[CONTACT_FLAGS];
+	for (;;) {
+		if (cap > (1ull << 31)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: overlaps: more than 2^31 label pairs");
+		keys.ensure(cap); cnt.ensure(cap); out_keys.ensure(cap); out_cnt.ensure(cap);
+		CKL_HIP(hipMemsetAsync(keys.p, 0xFF, cap * sizeof(unsigned long long), s));
+		CKL_HIP(hipMemsetAsync(cnt.p, 0, cap * sizeof(unsigned long long), s));
+		CKL_HIP(hipMemsetAsync(flags.p, 0, CONTACT_FLAGS * sizeof(uint32_t), s));
+		OverlapArgs oa;
+		oa.key_p = swapped ? d_key_b.p : d_key_a.p; oa.key_q = swapped ? d_key_a.p : d_key_b.p;
+		oa.comp_off_p = p.d_comp_off.p; oa.comp_off_q = q.d_comp_off.p;
+		oa.ncomp_p = p.d_ncomp_expect.p; oa.ncomp_q = q.d_ncomp_expect.p;
+		oa.sx = p.head.sx; oa.n_pixels = static_cast<uint32_t>(p.sxy);
+		oa.keys = keys.p; oa.counts = cnt.p;
+		oa.cap_mask = static_cast<uint32_t>(cap - 1);
+		oa.flags = flags.p;
+		hipLaunchKernelGGL(k_run_overlaps, dim3((std::max(max_a, max_b) + kContactRuns - 1) / kContactRuns, p.nslices), dim3(kContactBlock), 0, s, gq, rp, rq, oa);
+		hipLaunchKernelGGL(k_contacts_compact<1>, dim3(static_cast<uint32_t>((cap + kContactCompact - 1) / kContactCompact)), dim3(kBlock), 0, s,
+			keys.p, cnt.p, static_cast<uint32_t>(cap), out_keys.p, out_cnt.p, flags.p);
+		CKL_HIP(hipMemcpyAsync(hflags, flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+		CKL_HIP(hipStreamSynchronize(s));
+		CKL_HIP(hipGetLastError());
+		if (hflags[CONTACT_BADKEY]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: overlaps: a run or a component's label is outside the stream's tables");
+		if (!hflags[CONTACT_FULL]) break;
+		cap <<= 1;
+	}
+	const uint32_t n = hflags[CONTACT_COUNT];
+	auto k = host_out<unsigned long long>(std::max<uint32_t>(n, 1)), c = host_out<unsigned long long>(std::max<uint32_t>(n, 1));
+	if (n) {
+		CKL_HIP(hipMemcpyAsync(k.get(), out_keys.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		CKL_HIP(hipMemcpyAsync(c.get(), out_cnt.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		CKL_HIP(hipStreamSynchronize(s));
+	}
+	record_span(a);
+	// Indices into ascending label tables: the order of (index a, index b) is that of the label pairs.
+	// The entries are moved into buckets by a (one counting pass), then each bucket, a few entries that
+	// lie together, is sorted by b.
+	struct Entry { uint32_t kb; unsigned long long n; };
+	const uint32_t sh_a = swapped ? 0 : 32, sh_b = swapped ? 32 : 0;
+	std::vector<uint32_t> start(na + 1, 0);
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t ka = static_cast<uint32_t>(k[i] >> sh_a), kb = static_cast<uint32_t>(k[i] >> sh_b);
+		if (ka >= na || kb >= nb) throw Error(CKL_ERR_RUNTIME, "crackle_amd: overlaps: a pair outside the streams' label tables");
+		start[ka + 1]++;
+	}
+	for (uint32_t t = 0; t < na; t++) start[t + 1] += start[t];
+	auto entry = host_out<Entry>(std::max<uint32_t>(n, 1));      // (a cached block of the host pool)
+	{
+		std::vector<uint32_t> at(start.begin(), start.end() - 1);
+		for (uint32_t i = 0; i < n; i++) entry[at[static_cast<uint32_t>(k[i] >> sh_a)]++] = { static_cast<uint32_t>(k[i] >> sh_b), c[i] };
+	}
+	out.pairs = host_out<uint64_t>(std::max<uint64_t>(2ull * n, 1));
+	out.counts = host_out<uint64_t>(std::max<uint32_t>(n, 1));
+	out.n = n;
+	for (uint32_t t = 0; t < na; t++) {
+		if (start[t + 1] - start[t] > 1) std::sort(entry.get() + start[t], entry.get() + start[t + 1], [](const Entry& x, const Entry& y) { return x.kb < y.kb; });
+		const uint64_t va = a.stats_table[t];
+		for (uint32_t i = start[t]; i < start[t + 1]; i++) {
+			out.pairs[2ull * i] = va;
+			out.pairs[2ull * i + 1] = b.stats_table[entry[i].kb];
+			out.counts[i] = entry[i].n;
+		}
 	}
 }
 
@@ -1205,6 +1442,52 @@ int ckl_decoder_contacts(ckl_decoder* d, uint64_t** pairs, uint64_t** faces, uin
 		auto po = host_out<uint64_t>(std::max<uint64_t>(2 * n, 1)), fo = host_out<uint64_t>(std::max<uint64_t>(3 * n, 1));
 		if (n) { memcpy(po.get(), p.data(), 2 * n * 8); memcpy(fo.get(), f.data(), 3 * n * 8); }
 		*pairs = po.release(); *faces = fo.release(); *n_pairs = n;
+	});
+}
+
+// the table of decoder_overlaps handed to the caller (a block of one element each when it is empty)
+static void overlaps_out(OverlapTable& t, uint64_t** pairs, uint64_t** counts, uint64_t* n_pairs) {
+	if (!t.pairs) t.pairs = host_out<uint64_t>(1);
+	if (!t.counts) t.counts = host_out<uint64_t>(1);
+	*pairs = t.pairs.release(); *counts = t.counts.release(); *n_pairs = t.n;
+}
+
+int ckl_decoder_overlaps(ckl_decoder* a, ckl_decoder* b, uint64_t** pairs, uint64_t** counts, uint64_t* n_pairs) {
+	return guard([&] {
+		if (!a || !b || !pairs || !counts || !n_pairs) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*pairs = nullptr; *counts = nullptr; *n_pairs = 0;
+		OverlapTable t;
+		enter(b);
+		enter(a);
+		decoder_overlaps(*a, *b, t);
+		overlaps_out(t, pairs, counts, n_pairs);
+	});
+}
+
+int ckl_overlaps(
+	const uint8_t* buf1, uint64_t n1, const uint8_t* buf2, uint64_t n2,
+	int64_t z_start, int64_t z_end, int device, uint64_t** pairs, uint64_t** counts, uint64_t* n_pairs
+) {
+	return guard([&]() -> int {
+		if (!buf1 || !buf2 || !pairs || !counts || !n_pairs) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*pairs = nullptr; *counts = nullptr; *n_pairs = 0;
+		const Header h1 = Header::parse(buf1, n1), h2 = Header::parse(buf2, n2);
+		// from the two headers alone, before a device is touched
+		if (h1.sx != h2.sx || h1.sy != h2.sy || h1.sz != h2.sz)
+			throw Error(CKL_ERR_ARG, "crackle_amd: overlaps: the volumes differ in shape: " + std::to_string(h1.sx) + " x " + std::to_string(h1.sy) + " x " + std::to_string(h1.sz)
+				+ " and " + std::to_string(h2.sx) + " x " + std::to_string(h2.sy) + " x " + std::to_string(h2.sz));
+		int64_t zs, ze;
+		clamp_range(h1, z_start, z_end, zs, ze);
+		OverlapTable t;
+		if (static_cast<uint64_t>(h1.sx) * h1.sy != 0) {
+			DecoderPtr d1, d2;
+			int rc = open_decoder(buf1, n1, zs, ze, device, d1);
+			if (rc == CKL_OK) rc = open_decoder(buf2, n2, zs, ze, device, d2);
+			if (rc != CKL_OK) return rc;
+			decoder_overlaps(*d1, *d2, t);
+		}
+		overlaps_out(t, pairs, counts, n_pairs);
+		return CKL_OK;
 	});
 }
 

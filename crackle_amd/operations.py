@@ -1,7 +1,7 @@
 """Stream surgery on .ckl bytes without decoding — the slab merge the sharded encoder is built
 on, exposed with the reference's names (crackle/operations.py:424-662: zstack, zsplit,
 zshatter).  Host only (native: ckl_zstack / ckl_zsplit); FLAT label streams.  The consumers
-array_equal, mode_pooling_2x2x1, point_cloud, contacts and connected_components run on the device.
+array_equal, mode_pooling_2x2x1, point_cloud, contacts, overlaps and connected_components run on the device.
 The label edits remap, mask and mask_except rewrite header and label section on the host; recompress
 re-encodes a stream from its own labels on the device (ckl_recompress), without decoding a voxel."""
 import ctypes as C
@@ -238,6 +238,53 @@ def contacts(
   for (a, b), (nx, ny, nz) in zip(pairs.tolist(), faces.tolist()):
     out[(a, b)] = float(np.float32(nx * ax + ny * ay + nz * az))
   return out
+
+
+def _overlap_counts(binary_a: bytes, binary_b: bytes, z_start: int = 0, z_end: int = -1, device: int = 0):
+  """ckl_overlaps over the range: (pairs uint64 [n, 2], counts uint64 [n]), ascending by (a, b)."""
+  from .codec import _raise
+  a, b = bytes(binary_a), bytes(binary_b)
+  ha, hb = header(a), header(b)
+  if (ha.sx, ha.sy, ha.sz) != (hb.sx, hb.sy, hb.sz):
+    raise ValueError(
+      f"overlaps: the volumes differ in shape: {ha.sx} x {ha.sy} x {ha.sz} and {hb.sx} x {hb.sy} x {hb.sz}")
+  L = _lib.lib()
+  pp, cp, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+  try:
+    rc = L.ckl_overlaps(a, len(a), b, len(b), int(z_start), int(z_end), int(device), C.byref(pp), C.byref(cp), C.byref(n))
+    if rc != _lib.CKL_OK:
+      _raise(rc)
+    k = int(n.value)
+    if k == 0:
+      return np.zeros((0, 2), np.uint64), np.zeros(0, np.uint64)
+    pairs = np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_uint64)), shape=(k, 2)).copy()
+    counts = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_uint64)), shape=(k,)).copy()
+    return pairs, counts
+  finally:
+    for p in (pp, cp):
+      if p.value:
+        L.ckl_free(p)
+
+
+def overlaps(
+  binary_a: bytes, binary_b: bytes, z_start: int = 0, z_end: int = -1, device: int = 0,
+) -> Dict[Tuple[int, int], int]:
+  """The contingency table (overlap matrix) of two segmentations of one volume: {(a, b): voxels}
+  for every pair of labels for which some voxel has label a in binary_a and b in binary_b, the
+  input of variation of information, Rand indices, per-object IoU and split / merge counts.  The
+  reference has no such function.
+
+  Labels are uint64 values (signed labels sign-extended, so -3 is 2**64 - 3).  Label 0 is a label
+  like any other and nothing is dropped: the counts sum to the voxels of the range, the sums over b
+  are the voxel counts of binary_a and the sums over a those of binary_b.  The pair is ordered, not
+  min / max.  The streams must agree in shape (ValueError otherwise) and may differ in everything
+  else: dtype, FLAT or pin labels, format version, crack format, markov order, memory order.  The
+  z-range is clamped as by the other consumers; one without a slice raises RuntimeError.
+
+  Nothing is decoded to voxels: the device intersects the runs of the two streams row by row
+  (ckl_overlaps).  A damaged slice raises what decompress raises for that stream."""
+  pairs, counts = _overlap_counts(binary_a, binary_b, z_start, z_end, device)
+  return {(a, b): n for (a, b), n in zip(pairs.tolist(), counts.tolist())}
 
 
 def relabel_components(binary: bytes, new_ids) -> bytes:

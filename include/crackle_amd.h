@@ -206,6 +206,33 @@ int ckl_decoder_label_stats(
  * reference adds one float32 area per face instead; areas are the caller's (nx * wy * wz +
  * ny * wx * wz + nz * wx * wy). */
 int ckl_decoder_contacts(ckl_decoder* d, uint64_t** pairs, uint64_t** faces, uint64_t* n_pairs);
+/* The contingency table (overlap matrix) of two streams of one shape: for every pair of label values
+ * (a, b) for which some voxel has label a in the first stream and b in the second, the exact number of
+ * such voxels.  Voxels are matched by their (x, y, z); everything but the shape may differ between the
+ * streams (widths, signedness, FLAT or pin labels, format version, crack format, markov order, the
+ * fortran_order flag), each is read by its own header.  Labels are the values the decoder paints,
+ * sign-extended to 64 bits, as ckl_decoder_contacts and ckl_decoder_label_stats report them.  Label 0 is
+ * a label like any other and nothing is dropped: the counts sum to the voxels of the range, the sums over
+ * b are the voxel counts of the first stream and the sums over a those of the second.  The pair is
+ * ordered (a of the first stream, b of the second), not min / max.  Host outputs owned by the library,
+ * released with ckl_free: *pairs holds 2 * *n_pairs values, ascending by (a, b) as unsigned; *counts holds
+ * *n_pairs voxel counts.  Nothing is decoded to voxels and nothing is sorted on the device: both sessions
+ * run up to their run tables, then one kernel intersects the runs of the two streams row by row.
+ * Both sessions must be on one device and agree in sx, sy and the number of slices of their ranges (which
+ * may start at different z: slice i of the one is compared with slice i of the other), else CKL_ERR_ARG;
+ * null arguments are CKL_ERR_ARG.  A damaged slice of either range is reported as ckl_decompress of that
+ * stream reports it.  ckl_decoder_last_timing of `a` reports the device span of the whole operation; both
+ * sessions remain usable for any other entry point.  (No counterpart in the reference: it has no such
+ * entry.) */
+int ckl_decoder_overlaps(ckl_decoder* a, ckl_decoder* b, uint64_t** pairs, uint64_t** counts, uint64_t* n_pairs);
+/* The one-shot form of ckl_decoder_overlaps over slices [z_start, z_end) of both streams.  Streams that
+ * differ in sx, sy or sz are CKL_ERR_ARG, from the two headers alone (ckl_last_error names both shapes).
+ * The range is clamped by the rule of the other consumers (operations::get_szr, src/operations.hpp:54-72):
+ * a range without a slice, and sz == 0, are CKL_ERR_RUNTIME "crackle: Invalid range: zs - ze"; a stream
+ * with sx * sy == 0 and sz > 0 gives an empty table. */
+int ckl_overlaps(const uint8_t* buf1, uint64_t n1, const uint8_t* buf2, uint64_t n2,
+                 int64_t z_start, int64_t z_end, int device,
+                 uint64_t** pairs, uint64_t** counts, uint64_t* n_pairs);
 /* Random access to an x, y, z box: replaces CrackleArray.__getitem__ (crackle/array.py:257-285), which
  * decodes the whole slices of the z-range and lets numpy crop them.  The pipeline runs up to the run
  * tables and the component -> label map over the session's z-range (so a damaged slice of the range is

@@ -224,6 +224,9 @@ void wait_for_default_stream(hipStream_t s, hipEvent_t scratch_event);
 // stream order) the index of component i's value in uniq.  Everything but header and label section is
 // copied.  Host only; the result is malloc'd (release with ckl_free).
 uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len);
+// The same at the input's data width (dust, ckl_relabel_values): unsigned version 1 streams only, the values must
+// fit that width; the stream of an empty volume comes back as it is.
+uint8_t* relabel_stream_keep_width(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len);
 
 // markov model tables (src/markov.hpp:43-68, 222-266, 325-420)
 extern const uint8_t kMarkovLUT[24];

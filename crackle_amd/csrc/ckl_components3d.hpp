@@ -1,4 +1,5 @@
-// 3D connected components from the run tables: the device half of connected_components.
+// 3D connected components from the run tables: the device half of connected_components and of dust
+// (whose own kernels, k_cc_voxels / k_dust_mark / k_dust_keys, stand at the end).
 // (Included by ckl_operations.hip inside namespace ckl, after the contacts kernels whose run walk and
 // constants it shares: kContactBlock / kContactPer / kContactRuns, kNoKey.)
 //
@@ -44,6 +45,7 @@ struct LinkArgs {
 	uint32_t zero_key;               // table index of label 0 (kNoKey: absent): background, never linked
 	uint32_t sx, sy, n_pixels;
 	uint32_t connectivity;           // 6, 18 or 26
+	uint32_t binary;                 // nonzero (dust's binary_image): every two foreground neighbours are linked, whatever their labels
 	uint32_t* parent;                // [total_comp]
 	uint32_t* flags;                 // [CC_FLAGS]
 };
@@ -89,6 +91,11 @@ __device__ __forceinline__ void cc_unite(uint32_t* parent, uint32_t& a, uint32_t
 	}
 }
 
+// are a component of label index ka (never label 0's) and a neighbouring one of label index kb one piece?
+__device__ __forceinline__ bool cc_joined(const LinkArgs& la, uint32_t ka, uint32_t kb) {
+	return la.binary ? kb != la.zero_key : kb == ka;
+}
+
 // links between the run's pixels [lo, hi] (a member ga of its component's set, label index ka) and the runs of row
 // y of slice zj; skip: the run's own component where zj is its slice (kNoKey otherwise)
 __device__ __forceinline__ void link_row(
@@ -108,7 +115,7 @@ __device__ __forceinline__ void link_row(
 		if (ccj != skip) {
 			const uint32_t kj = ccj < nce_j ? key_j[ccj] : kNoKey;
 			if (kj == kNoKey) atomicOr(la.flags + CC_BADKEY, 1u);
-			else if (kj == ka && off_j + ccj != last) {
+			else if (cc_joined(la, ka, kj) && off_j + ccj != last) {
 				last = off_j + ccj;
 				cc_unite(la.parent, ga, last);
 			}
@@ -155,7 +162,7 @@ static __global__ void __launch_bounds__(kContactBlock) k_run_links(
 			if (cc2 != cc) {
 				const uint32_t kb = cc2 < nce ? key_z[cc2] : kNoKey;
 				if (kb == kNoKey) atomicOr(la.flags + CC_BADKEY, 1u);
-				else if (kb == ka) { last = off + cc2; cc_unite(la.parent, ga, last); }
+				else if (cc_joined(la, ka, kb)) { last = off + cc2; cc_unite(la.parent, ga, last); }
 			}
 		}
 		const uint32_t xl = x0 ? x0 - 1 : 0u, xr = min(x1 + 1, la.sx - 1);      // [x0 - 1, x1 + 1] inside the slice
@@ -267,5 +274,132 @@ static __global__ void __launch_bounds__(kBlock) k_cc_keys(
 	// the buffer is padded to a multiple of four keys
 	if (n_unique <= 0xFFull) *reinterpret_cast<uchar4*>(keys + c0) = make_uchar4(static_cast<unsigned char>(k[0]), static_cast<unsigned char>(k[1]), static_cast<unsigned char>(k[2]), static_cast<unsigned char>(k[3]));
 	else if (n_unique <= 0xFFFFull) *reinterpret_cast<ushort4*>(keys + 2ull * c0) = make_ushort4(static_cast<unsigned short>(k[0]), static_cast<unsigned short>(k[1]), static_cast<unsigned short>(k[2]), static_cast<unsigned short>(k[3]));
+	else *reinterpret_cast<uint4*>(keys + 4ull * c0) = make_uint4(k[0], k[1], k[2], k[3]);
+}
+
+// ------------------------------------------------------------------------------
+// dust: components below (or, inverted, at or above) a voxel count lose their label.
+//
+//   k_cc_voxels    one run per thread (the layout of k_run_links): every foreground run adds its
+//                  length to the counter of its component's root.  The runs of a workgroup share few
+//                  roots, so the sums are taken in an LDS open-addressing table first (key: the root,
+//                  a 32-bit counter: a workgroup's runs lie in one slice and do not intersect, so
+//                  their lengths sum to less than 2^32) and flushed with one 64-bit atomic per root.
+//                  A root that finds no room in the LDS table adds to its global counter directly:
+//                  the global table is indexed by root, it cannot fill.
+//   k_dust_mark    per component: kept ones mark their label as used, removed roots are counted
+//   k_dust_keys    every component's key into the new unique list, packed at the key width
+// ------------------------------------------------------------------------------
+constexpr uint32_t kVoxelLds = 1024;          // LDS table entries (power of two)
+constexpr uint32_t kVoxelLdsBits = 10;
+constexpr uint32_t kVoxelProbes = 32;         // LDS probes before a run goes to the global counter
+static_assert(kVoxelLds == 1u << kVoxelLdsBits, "the hash keeps kVoxelLdsBits bits");
+
+struct VoxelArgs {
+	const uint32_t* comp_key;        // [total_comp] label table index of every component (kNoKey: not in the table)
+	uint32_t zero_key;               // table index of label 0 (kNoKey: absent): not counted
+	uint32_t n_pixels;
+	const uint32_t* root;            // [total_comp] k_cc_flatten's roots
+	unsigned long long* voxels;      // [total_comp] voxels of the set, at its root; zeroed
+	uint32_t* flags;                 // [CC_FLAGS]
+};
+
+// grid = (ceil(most runs of a slice / kContactRuns), nslices), block = kContactBlock
+static __global__ void __launch_bounds__(kContactBlock) k_cc_voxels(
+	RunArrays r, const uint64_t* __restrict__ comp_off, const uint32_t* __restrict__ ncomp_expect, VoxelArgs va
+) {
+	__shared__ uint32_t s_key[kVoxelLds];
+	__shared__ uint32_t s_cnt[kVoxelLds];
+	const uint32_t zi = blockIdx.y;
+	const uint32_t n = r.nruns[zi];
+	const uint32_t i0 = blockIdx.x * kContactRuns;
+	if (i0 >= n) return;
+	for (uint32_t k = threadIdx.x; k < kVoxelLds; k += kContactBlock) { s_key[k] = kNoKey; s_cnt[k] = 0; }
+	__syncthreads();
+	const uint64_t rb = r.rbase[zi];
+	const uint32_t nce = ncomp_expect[zi];
+	const uint32_t off = static_cast<uint32_t>(comp_off[zi]);
+	const uint32_t* key_z = va.comp_key + off;
+	for (uint32_t k = 0; k < kContactPer; k++) {
+		const uint32_t i = i0 + k * kContactBlock + threadIdx.x;
+		if (i >= n) break;
+		const uint32_t a = r.run_start[rb + i];
+		const uint32_t b = i + 1 < n ? r.run_start[rb + i + 1] : va.n_pixels;
+		const uint32_t cc = r.run_cc[rb + i];
+		const uint32_t ka = cc < nce ? key_z[cc] : kNoKey;
+		if (ka == kNoKey) { atomicOr(va.flags + CC_BADKEY, 1u); continue; }
+		if (ka == va.zero_key || b <= a) continue;
+		const uint32_t root = va.root[off + cc];      // a component id: never kNoKey
+		const uint32_t len = b - a;
+		const uint32_t h = (root * 0x9E3779B1u) >> (32u - kVoxelLdsBits);
+		bool placed = false;
+		for (uint32_t p = 0; p < kVoxelProbes && !placed; p++) {
+			const uint32_t slot = (h + p) & (kVoxelLds - 1);
+			uint32_t cur = s_key[slot];      // a slot changes once, from empty to its key: a stale read is settled by the CAS
+			if (cur == kNoKey) {
+				cur = atomicCAS(s_key + slot, kNoKey, root);
+				if (cur == kNoKey) cur = root;
+			}
+			if (cur == root) { atomicAdd(s_cnt + slot, len); placed = true; }
+		}
+		if (!placed) atomicAdd(va.voxels + root, static_cast<unsigned long long>(len));
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < kVoxelLds; k += kContactBlock) {
+		const uint32_t root = s_key[k];
+		if (root != kNoKey) atomicAdd(va.voxels + root, static_cast<unsigned long long>(s_cnt[k]));
+	}
+}
+
+struct DustArgs {
+	const uint32_t* root;                 // [n]
+	const uint32_t* comp_key;             // [n]
+	const unsigned long long* voxels;     // [n], valid at the roots
+	uint32_t zero_key, n;
+	unsigned long long threshold;
+	uint32_t invert;
+};
+
+// does component c (label index key, not kNoKey) lose its label?
+__device__ __forceinline__ bool dust_removed(const DustArgs& da, uint32_t c, uint32_t key) {
+	return key != da.zero_key && ((da.voxels[da.root[c]] < da.threshold) != (da.invert != 0));
+}
+
+// used[key] = 1 for the label of every component that keeps it (label 0's included);
+// flags[CC_COUNT] += the 3D components removed (their roots)
+static __global__ void __launch_bounds__(kBlock) k_dust_mark(DustArgs da, uint32_t n_table, uint8_t* __restrict__ used, uint32_t* __restrict__ flags) {
+	__shared__ uint32_t s_red[kWaves];
+	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+	uint32_t cnt = 0;
+	if (c < da.n) {
+		const uint32_t key = da.comp_key[c];
+		if (key >= n_table) atomicOr(flags + CC_BADKEY, 1u);
+		else if (!dust_removed(da, c, key)) used[key] = 1;
+		else if (da.root[c] == c) cnt = 1;
+	}
+	cnt = block_sum(cnt, s_red);
+	if (threadIdx.x == 0 && cnt) atomicAdd(flags + CC_COUNT, cnt);
+}
+
+// keys[c] = new_index[label index of c], or 0 (the place of label 0 in an ascending unsigned list) where c
+// is removed, at the width of the new list's length: four components per thread, one store
+static __global__ void __launch_bounds__(kBlock) k_dust_keys(
+	DustArgs da, uint32_t n_table, const uint32_t* __restrict__ new_index, uint32_t n_unique, uint8_t* __restrict__ keys
+) {
+	const uint32_t c0 = (blockIdx.x * kBlock + threadIdx.x) * 4u;
+	if (c0 >= da.n) return;
+	uint32_t k[4];
+#pragma unroll
+	for (uint32_t j = 0; j < 4; j++) {
+		const uint32_t c = c0 + j;
+		k[j] = 0;
+		if (c < da.n) {
+			const uint32_t key = da.comp_key[c];
+			if (key < n_table && !dust_removed(da, c, key)) k[j] = new_index[key];
+		}
+	}
+	// the buffer is padded to a multiple of four keys
+	if (n_unique <= 0xFFu) *reinterpret_cast<uchar4*>(keys + c0) = make_uchar4(static_cast<unsigned char>(k[0]), static_cast<unsigned char>(k[1]), static_cast<unsigned char>(k[2]), static_cast<unsigned char>(k[3]));
+	else if (n_unique <= 0xFFFFu) *reinterpret_cast<ushort4*>(keys + 2ull * c0) = make_ushort4(static_cast<unsigned short>(k[0]), static_cast<unsigned short>(k[1]), static_cast<unsigned short>(k[2]), static_cast<unsigned short>(k[3]));
 	else *reinterpret_cast<uint4*>(keys + 4ull * c0) = make_uint4(k[0], k[1], k[2], k[3]);
 }

@@ -1007,46 +1007,60 @@ struct Components3D {
 	std::vector<uint64_t> root_labels;
 };
 
-void decoder_connected_components(ckl_decoder& d, int connectivity, bool want_labels, Components3D& out) {
+// The front that connected_components and dust share: one pipeline run up to the run tables, the
+// label table, every component's label index, the links, the roots.  flags is cleared before the
+// links and holds CC_BADKEY after them (read together with what the caller's kernels add).
+struct ComponentLinks {
+	DevBuf<uint32_t> comp_key, parent, root, flags;
+	uint32_t nc = 0, zero_key = kNoKey, max_runs = 0;
+};
+
+void link_components(ckl_decoder& d, int connectivity, bool binary_image, const char* what, ComponentLinks& L) {
 	const Header& h = d.head;
 	hipStream_t s = d.stream;
-	const uint32_t ns = d.nslices;
 	decoder_run(d, { Goal::TABLES });
 	ensure_label_table(d);
 	const uint32_t n_table = static_cast<uint32_t>(d.stats_table.size());
 	if (d.total_comp == 0 || n_table == 0) throw Error(CKL_ERR_RUNTIME, "crackle: label section is malformed or corrupted.");
-	if (d.total_comp > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: connected_components: more than 2^32 - 1 components");
-	const uint32_t nc = static_cast<uint32_t>(d.total_comp);
-	DevBuf<uint32_t> d_comp_key, parent, root, number, blk, flags;
-	DevBuf<uint64_t> root_label;
-	DevBuf<uint8_t> keys;
-	const uint32_t max_runs = component_keys(d, d_comp_key);
-
+	if (d.total_comp > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, std::string("crackle_amd: ") + what + ": more than 2^32 - 1 components");
+	const uint32_t nc = L.nc = static_cast<uint32_t>(d.total_comp);
+	L.max_runs = component_keys(d, L.comp_key);
 	const RunGeom g = run_geom(d);
 	const RunArrays ra = run_arrays(d);
-
-	const uint32_t nb = (nc + kCcTile - 1) / kCcTile;
-	parent.ensure(nc); root.ensure(nc); number.ensure(nc); blk.ensure(nb); flags.ensure(CC_FLAGS);
-	if (want_labels) root_label.ensure(nc);
-	keys.ensure(4ull * nb * kCcTile);      // the widest keys, padded to whole tiles
-	CKL_HIP(hipMemsetAsync(flags.p, 0, CC_FLAGS * sizeof(uint32_t), s));
+	L.parent.ensure(nc); L.root.ensure(nc); L.flags.ensure(CC_FLAGS);
+	CKL_HIP(hipMemsetAsync(L.flags.p, 0, CC_FLAGS * sizeof(uint32_t), s));
 	LinkArgs la;
-	la.comp_key = d_comp_key.p;
-	la.zero_key = d.stats_table[0] == 0 ? 0u : kNoKey;
+	la.comp_key = L.comp_key.p;
+	la.zero_key = L.zero_key = d.stats_table[0] == 0 ? 0u : kNoKey;
 	la.sx = h.sx; la.sy = h.sy; la.n_pixels = static_cast<uint32_t>(d.sxy);
 	la.connectivity = static_cast<uint32_t>(connectivity);
-	la.parent = parent.p; la.flags = flags.p;
-	hipLaunchKernelGGL(k_cc_init, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, parent.p, nc);
-	if (max_runs) hipLaunchKernelGGL(k_run_links, dim3((max_runs + kContactRuns - 1) / kContactRuns, ns), dim3(kContactBlock), 0, s,
+	la.binary = binary_image ? 1u : 0u;
+	la.parent = L.parent.p; la.flags = L.flags.p;
+	hipLaunchKernelGGL(k_cc_init, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, L.parent.p, nc);
+	if (L.max_runs) hipLaunchKernelGGL(k_run_links, dim3((L.max_runs + kContactRuns - 1) / kContactRuns, d.nslices), dim3(kContactBlock), 0, s,
 		g, ra, d.d_comp_off.p, d.d_ncomp_expect.p, la);
-	hipLaunchKernelGGL(k_cc_flatten, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, parent.p, nc, root.p);
-	hipLaunchKernelGGL(k_cc_count, dim3(nb), dim3(kBlock), 0, s, root.p, d_comp_key.p, la.zero_key, nc, blk.p, flags.p);
-	hipLaunchKernelGGL(k_cc_offsets, dim3(1), dim3(kBlock), 0, s, blk.p, nb, flags.p);
-	hipLaunchKernelGGL(k_cc_number, dim3(nb), dim3(kBlock), 0, s, root.p, d_comp_key.p, la.zero_key, nc, blk.p, number.p,
+	hipLaunchKernelGGL(k_cc_flatten, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, L.parent.p, nc, L.root.p);
+}
+
+void decoder_connected_components(ckl_decoder& d, int connectivity, bool want_labels, Components3D& out) {
+	hipStream_t s = d.stream;
+	ComponentLinks L;
+	link_components(d, connectivity, false, "connected_components", L);
+	const uint32_t nc = L.nc;
+	DevBuf<uint32_t> number, blk;
+	DevBuf<uint64_t> root_label;
+	DevBuf<uint8_t> keys;
+	const uint32_t nb = (nc + kCcTile - 1) / kCcTile;
+	number.ensure(nc); blk.ensure(nb);
+	if (want_labels) root_label.ensure(nc);
+	keys.ensure(4ull * nb * kCcTile);      // the widest keys, padded to whole tiles
+	hipLaunchKernelGGL(k_cc_count, dim3(nb), dim3(kBlock), 0, s, L.root.p, L.comp_key.p, L.zero_key, nc, blk.p, L.flags.p);
+	hipLaunchKernelGGL(k_cc_offsets, dim3(1), dim3(kBlock), 0, s, blk.p, nb, L.flags.p);
+	hipLaunchKernelGGL(k_cc_number, dim3(nb), dim3(kBlock), 0, s, L.root.p, L.comp_key.p, L.zero_key, nc, blk.p, number.p,
 		d.d_label_map.p, want_labels ? reinterpret_cast<uint64_t*>(root_label.p) : nullptr);
-	hipLaunchKernelGGL(k_cc_keys, dim3(nb), dim3(kBlock), 0, s, root.p, d_comp_key.p, la.zero_key, nc, number.p, flags.p, keys.p);
+	hipLaunchKernelGGL(k_cc_keys, dim3(nb), dim3(kBlock), 0, s, L.root.p, L.comp_key.p, L.zero_key, nc, number.p, L.flags.p, keys.p);
 	uint32_t hflags[CC_FLAGS];
-	CKL_HIP(hipMemcpyAsync(hflags, flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipMemcpyAsync(hflags, L.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
 	CKL_HIP(hipStreamSynchronize(s));
 	CKL_HIP(hipGetLastError());
 	if (hflags[CC_BADKEY]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: connected_components: a component's label is not in the stream's label table");
@@ -1057,6 +1071,72 @@ void decoder_connected_components(ckl_decoder& d, int connectivity, bool want_la
 	CKL_HIP(hipMemcpyAsync(out.keys.data(), keys.p, out.keys.size(), hipMemcpyDeviceToHost, s));
 	out.root_labels.resize(want_labels ? out.n_components : 0);
 	if (want_labels && out.n_components) CKL_HIP(hipMemcpyAsync(out.root_labels.data(), root_label.p, out.n_components * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+	record_span(d);
+}
+
+// dust over the whole stream (ckl_components3d.hpp): the links of connected_components (by label, or
+// binary_image: between any two foreground voxels), the voxels of every set (k_cc_voxels), then the
+// label edit: a component of a set below the threshold (invert: at or above it) gets label 0.  The
+// new unique list is made on the host from one byte per label of the old one; the device packs the
+// keys.  uniq: the new list, ascending; keys: one key per component at key_width bytes.
+struct Dust {
+	std::vector<uint64_t> uniq;
+	std::vector<uint8_t> keys;
+	int key_width = 1;
+	uint64_t n_removed = 0;
+};
+
+void decoder_dust(ckl_decoder& d, uint64_t threshold, int connectivity, bool binary_image, bool invert, Dust& out) {
+	hipStream_t s = d.stream;
+	ComponentLinks L;
+	link_components(d, connectivity, binary_image, "dust", L);
+	const uint32_t nc = L.nc;
+	const uint32_t n_table = static_cast<uint32_t>(d.stats_table.size());
+	DevBuf<unsigned long long> voxels;
+	DevBuf<uint8_t> used, keys;
+	DevBuf<uint32_t> new_index;
+	voxels.ensure(nc); used.ensure(n_table);
+	CKL_HIP(hipMemsetAsync(voxels.p, 0, nc * sizeof(unsigned long long), s));
+	CKL_HIP(hipMemsetAsync(used.p, 0, n_table, s));
+	VoxelArgs va;
+	va.comp_key = L.comp_key.p; va.zero_key = L.zero_key;
+	va.n_pixels = static_cast<uint32_t>(d.sxy);
+	va.root = L.root.p; va.voxels = voxels.p; va.flags = L.flags.p;
+	if (L.max_runs) hipLaunchKernelGGL(k_cc_voxels, dim3((L.max_runs + kContactRuns - 1) / kContactRuns, d.nslices), dim3(kContactBlock), 0, s,
+		run_arrays(d), d.d_comp_off.p, d.d_ncomp_expect.p, va);
+	DustArgs da;
+	da.root = L.root.p; da.comp_key = L.comp_key.p; da.voxels = voxels.p;
+	da.zero_key = L.zero_key; da.n = nc;
+	da.threshold = threshold; da.invert = invert ? 1u : 0u;
+	hipLaunchKernelGGL(k_dust_mark, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, da, n_table, used.p, L.flags.p);
+	uint32_t hflags[CC_FLAGS];
+	std::vector<uint8_t> hused(n_table);
+	CKL_HIP(hipMemcpyAsync(hflags, L.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipMemcpyAsync(hused.data(), used.p, n_table, hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	CKL_HIP(hipGetLastError());
+	if (hflags[CC_BADKEY]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: dust: a component's label is not in the stream's label table");
+	out.n_removed = hflags[CC_COUNT];
+	// the labels still in use, ascending as the table is; 0 in front when something was removed and it was not there
+	const bool add_zero = out.n_removed != 0 && !(L.zero_key != kNoKey && hused[L.zero_key]);
+	std::vector<uint32_t> index(n_table, 0);
+	out.uniq.clear();
+	if (add_zero) out.uniq.push_back(0);
+	for (uint32_t k = 0; k < n_table; k++) {
+		if (!hused[k]) continue;
+		index[k] = static_cast<uint32_t>(out.uniq.size());
+		out.uniq.push_back(d.stats_table[k]);
+	}
+	if (out.uniq.empty() || out.uniq.size() > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: dust: the new label list is empty or holds 2^32 labels or more");
+	out.key_width = byte_width(out.uniq.size());
+	upload(new_index, index, s);
+	const uint32_t nq = (nc + 3) / 4;      // four components per thread
+	keys.ensure(16ull * nq);              // the widest keys, padded to a multiple of four
+	hipLaunchKernelGGL(k_dust_keys, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, s, da, n_table, new_index.p, static_cast<uint32_t>(out.uniq.size()), keys.p);
+	out.keys.resize(static_cast<size_t>(nc) * out.key_width);
+	CKL_HIP(hipMemcpyAsync(out.keys.data(), keys.p, out.keys.size(), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	CKL_HIP(hipGetLastError());
 	record_span(d);
 }
 
@@ -1522,6 +1602,33 @@ int ckl_connected_components(
 		*out = relabel_stream(buf, n, uniq, cc.keys.data(), cc.key_width, cc.keys.size() / cc.key_width, out_len);
 		if (component_labels) *component_labels = lo.release();
 		if (n_components) *n_components = cc.n_components;
+		return CKL_OK;
+	});
+}
+
+int ckl_dust(
+	const uint8_t* buf, uint64_t n, uint64_t threshold, int connectivity, int flags, int device,
+	uint8_t** out, uint64_t* out_len, uint64_t* n_removed
+) {
+	return guard([&]() -> int {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*out = nullptr; *out_len = 0;
+		if (n_removed) *n_removed = 0;
+		if (connectivity != 6 && connectivity != 18 && connectivity != 26) throw Error(CKL_ERR_ARG, "crackle_amd: dust: connectivity must be 6, 18 or 26");
+		if (flags & ~(CKL_DUST_BINARY_IMAGE | CKL_DUST_INVERT)) throw Error(CKL_ERR_ARG, "crackle_amd: dust: unknown flags");
+		const Header h = Header::parse(buf, n);
+		if (h.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: dust: version 0 streams have no crack crcs to carry over: recompress() first");
+		if (h.is_signed) throw Error(CKL_ERR_ARG, "crackle_amd: dust: signed streams are not supported");
+		Dust du;
+		if (h.voxels() != 0) {      // (an empty volume comes back as it is, from the host alone)
+			DecoderPtr d;
+			const int rc = open_decoder(buf, n, 0, -1, device, d);
+			if (rc != CKL_OK) return rc;
+			enter(d.get());
+			decoder_dust(*d, threshold, connectivity, (flags & CKL_DUST_BINARY_IMAGE) != 0, (flags & CKL_DUST_INVERT) != 0, du);
+		}
+		*out = relabel_stream_keep_width(buf, n, du.uniq, du.keys.data(), du.key_width, du.keys.size() / du.key_width, out_len);
+		if (n_removed) *n_removed = du.n_removed;
 		return CKL_OK;
 	});
 }

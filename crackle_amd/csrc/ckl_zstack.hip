@@ -241,11 +241,24 @@ static const uint8_t* component_counts(const Header& h, const uint8_t* buf, uint
 	return lb + offset;
 }
 
-uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len) {
+// keep_width: the result keeps the input's data width (unsigned inputs only; an empty volume comes back as it
+// is); otherwise it is uint32 whatever the input was
+static uint8_t* relabel_write(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, bool keep_width, uint64_t* out_len) {
 	const Header h0 = Header::parse(buf, n);
 	Header h = h0;
 	h.format_version = 1;
-	h.data_width = 4;
+	if (keep_width) {
+		if (h0.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: version 0 streams have no crack crcs to carry over: recompress() first");
+		if (h0.is_signed) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: signed streams are not supported");
+		if (h0.voxels() == 0) {
+			uint8_t* o = static_cast<uint8_t*>(malloc(n ? n : 1));
+			if (!o) throw Error(CKL_ERR_RUNTIME, "crackle_amd: out of host memory");
+			memcpy(o, buf, n);
+			*out_len = n;
+			return o;
+		}
+	}
+	else h.data_width = 4;
 	h.is_signed = false;
 	h.label_format = FLAT;
 	h.is_sorted = true;
@@ -266,7 +279,9 @@ uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64
 	uint64_t total_comp = 0;
 	const uint8_t* counts = component_counts(h0, buf, n, &total_comp);
 	if (n_keys != total_comp) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: " + std::to_string(n_keys) + " ids for the stream's " + std::to_string(total_comp) + " components");
-	if (uniq.empty() || uniq.back() > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: component ids must lie in 0 .. 2^32 - 1");
+	if (!keep_width && (uniq.empty() || uniq.back() > 0xFFFFFFFFull)) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: component ids must lie in 0 .. 2^32 - 1");
+	if (keep_width && (uniq.empty() || byte_width(uniq.back()) > h0.data_width))
+		throw Error(CKL_ERR_ARG, "crackle_amd: relabel: a value does not fit the stream's data width of " + std::to_string(h0.data_width) + " bytes");
 	if (key_width != byte_width(uniq.size())) throw Error(CKL_ERR_ARG, "crackle_amd: relabel: key width does not match the number of values");
 	const int sw = h.stored_data_width;
 	const uint64_t cwb = static_cast<uint64_t>(byte_width(static_cast<uint64_t>(h.sx) * h.sy)) * h.sz;
@@ -295,29 +310,57 @@ uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64
 	return o;
 }
 
+uint8_t* relabel_stream(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len) {
+	return relabel_write(buf, n, uniq, keys, key_width, n_keys, false, out_len);
+}
+
+uint8_t* relabel_stream_keep_width(const uint8_t* buf, uint64_t n, const std::vector<uint64_t>& uniq, const uint8_t* keys, int key_width, uint64_t n_keys, uint64_t* out_len) {
+	return relabel_write(buf, n, uniq, keys, key_width, n_keys, true, out_len);
+}
+
+// ascending set of `values` and, per value, its index in the set at the set's key width
+static void keys_of_values(const uint64_t* values, uint64_t n_values, std::vector<uint64_t>& uniq, std::vector<uint8_t>& keys, int& kw) {
+	uniq.assign(values, values + n_values);
+	std::sort(uniq.begin(), uniq.end());
+	uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+	kw = byte_width(uniq.size());
+	keys.clear();
+	keys.reserve(n_values * kw);
+	// values are mostly 0 .. N: a direct table where they are dense, a search where they are not
+	const bool dense = !uniq.empty() && uniq.back() < 2 * uniq.size() + 16;
+	std::vector<uint32_t> index;
+	if (dense) {
+		index.resize(uniq.back() + 1);
+		for (size_t i = 0; i < uniq.size(); i++) index[uniq[i]] = static_cast<uint32_t>(i);
+	}
+	for (uint64_t i = 0; i < n_values; i++) {
+		const uint64_t k = dense ? index[values[i]] : static_cast<uint64_t>(std::lower_bound(uniq.begin(), uniq.end(), values[i]) - uniq.begin());
+		put_le(keys, k, kw);
+	}
+}
+
 }  // namespace ckl
+
+extern "C" int ckl_relabel_values(const uint8_t* buf, uint64_t n, const uint64_t* values, uint64_t n_values, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len || (!values && n_values)) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*out = nullptr; *out_len = 0;
+		std::vector<uint64_t> uniq;
+		std::vector<uint8_t> keys;
+		int kw = 1;
+		keys_of_values(values, n_values, uniq, keys, kw);
+		*out = relabel_stream_keep_width(buf, n, uniq, keys.data(), kw, n_values, out_len);
+	});
+}
 
 extern "C" int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint64_t* new_ids, uint64_t n_ids, uint8_t** out, uint64_t* out_len) {
 	return guard([&] {
 		if (!buf || !out || !out_len || (!new_ids && n_ids)) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		*out = nullptr; *out_len = 0;
-		std::vector<uint64_t> uniq(new_ids, new_ids + n_ids);
-		std::sort(uniq.begin(), uniq.end());
-		uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-		const int kw = byte_width(uniq.size());
+		std::vector<uint64_t> uniq;
 		std::vector<uint8_t> keys;
-		keys.reserve(n_ids * kw);
-		// ids are mostly 0 .. N: a direct table where they are dense, a search where they are not
-		const bool dense = !uniq.empty() && uniq.back() < 2 * uniq.size() + 16;
-		std::vector<uint32_t> index;
-		if (dense) {
-			index.resize(uniq.back() + 1);
-			for (size_t i = 0; i < uniq.size(); i++) index[uniq[i]] = static_cast<uint32_t>(i);
-		}
-		for (uint64_t i = 0; i < n_ids; i++) {
-			const uint64_t k = dense ? index[new_ids[i]] : static_cast<uint64_t>(std::lower_bound(uniq.begin(), uniq.end(), new_ids[i]) - uniq.begin());
-			put_le(keys, k, kw);
-		}
+		int kw = 1;
+		keys_of_values(new_ids, n_ids, uniq, keys, kw);
 		*out = relabel_stream(buf, n, uniq, keys.data(), kw, n_ids, out_len);
 	});
 }

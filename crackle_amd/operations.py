@@ -1,7 +1,7 @@
 """Stream surgery on .ckl bytes without decoding — the slab merge the sharded encoder is built
 on, exposed with the reference's names (crackle/operations.py:424-662: zstack, zsplit,
 zshatter).  Host only (native: ckl_zstack / ckl_zsplit); FLAT label streams.  The consumers
-array_equal, mode_pooling_2x2x1, point_cloud, contacts, overlaps and connected_components run on the device.
+array_equal, mode_pooling_2x2x1, point_cloud, contacts, overlaps, connected_components and dust run on the device.
 The label edits remap, mask and mask_except rewrite header and label section on the host; recompress
 re-encodes a stream from its own labels on the device (ckl_recompress), without decoding a voxel."""
 import ctypes as C
@@ -362,6 +362,70 @@ def connected_components(
     L.ckl_free(out)
     if lab.value:
       L.ckl_free(lab)
+
+
+def relabel_values(binary: bytes, values) -> bytes:
+  """The stream with 2D component i of its slices (stream order) given the label values[i], at the input's data
+  width, as the canonical FLAT stream dust() documents (ckl_relabel_values; host only)."""
+  b = bytes(binary)
+  vals = np.ascontiguousarray(values, dtype=np.uint64)
+  out, n = C.c_void_p(), C.c_uint64()
+  if _lib.lib().ckl_relabel_values(b, len(b), vals.ctypes.data, vals.size, C.byref(out), C.byref(n)) != _lib.CKL_OK:
+    raise ValueError(_lib.last_error())
+  return _take(out, n)
+
+
+def dust(
+  binary: bytes, threshold: int, connectivity: int = 26, binary_image: bool = False,
+  invert: bool = False, return_removed: bool = False, device: int = 0,
+) -> Union[bytes, Tuple[bytes, int]]:
+  """The stream without its "dust" (cc3d's dust; the reference has none): every voxel of a 3D component with fewer
+  than `threshold` voxels becomes 0, nothing else changes.  With return_removed: also the number of 3D components
+  set to 0.
+
+  A component is what connected_components documents: a maximal set of voxels with the same nonzero label joined
+  by 6-, 18- or 26-neighbour steps; equality is by label, so touching 2D components that share a label after
+  remap() are one component.  binary_image=True groups all nonzero voxels instead, whatever their labels; only the
+  grouping changes, survivors keep their own labels.  invert=True removes the components with `threshold` voxels
+  or more instead.  A threshold of 0 or 1 without invert removes nothing.
+
+  Nothing is decoded to voxels and no crack changes: the device links the 2D components of the slices as
+  connected_components does, sums the run lengths of every 3D component and rewrites the labels (ckl_dust).  The
+  result is a canonical FLAT stream, format version 1, as remap() documents its result: the unique list ascending
+  without duplicates, without the labels nothing carries any more and with 0 when something was removed, the keys
+  at the width of the new count, the stored width from the largest remaining label, is_sorted set.  Data width
+  and fortran_order flag are the input's; z-index, markov model, crack codes and slice crcs are the input's bytes.
+  If nothing is removed and the input is a FLAT version 1 stream from compress(), the output is the input.
+  Removed components keep their cracks ("false boundaries"): recompress(dust(b)) is the whole clean-up pass.
+
+  FLAT and pin label streams are accepted (a pin stream comes back FLAT).  Format version 0 raises ValueError,
+  signed streams TypeError, a negative threshold or one of 2^64 or more ValueError, a connectivity other than
+  6, 18 or 26 ValueError.  The stream of an empty volume is returned as it is, without a device.  A damaged slice
+  raises what decompress raises for it."""
+  from .codec import _raise
+  if connectivity not in (6, 18, 26):
+    raise ValueError(f"dust: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  threshold = int(threshold)
+  if threshold < 0:
+    raise ValueError(f"dust: threshold must not be negative. Got: {threshold}")
+  if threshold >= 1 << 64:
+    raise ValueError(f"dust: threshold must be below 2^64. Got: {threshold}")
+  b = bytes(binary)
+  head = header(b)
+  if head.format_version == 0:
+    raise ValueError("dust: format version 0 streams have no crack crcs to carry over; recompress() first.")
+  if head.signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  if head.voxels() == 0:
+    return (b, 0) if return_removed else b
+  flags = (_lib.CKL_DUST_BINARY_IMAGE if binary_image else 0) | (_lib.CKL_DUST_INVERT if invert else 0)
+  out, n, removed = C.c_void_p(), C.c_uint64(), C.c_uint64()
+  rc = _lib.lib().ckl_dust(b, len(b), threshold, int(connectivity), flags, int(device), C.byref(out), C.byref(n),
+                           C.byref(removed) if return_removed else None)
+  if rc != _lib.CKL_OK:
+    _raise(rc)
+  result = _take(out, n)
+  return (result, int(removed.value)) if return_removed else result
 
 
 # ---- label edits: remap / mask / mask_except on the host, recompress on the device ------------------------------------

@@ -528,6 +528,33 @@ int ckl_connected_components(
  * with ckl_free. */
 int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint64_t* new_ids, uint64_t n_ids, uint8_t** out, uint64_t* out_len);
 
+/* Removes the "dust" of a stream (cc3d's dust; the reference has no such function): every voxel of a 3D
+ * component (as ckl_connected_components defines them: one label, 6 / 18 / 26 neighbours) with fewer than
+ * `threshold` voxels becomes 0.  flags: CKL_DUST_BINARY_IMAGE groups all nonzero voxels into components
+ * whatever their labels (survivors keep their own labels), CKL_DUST_INVERT removes the components with
+ * `threshold` voxels or more instead.  No voxel is decoded and no crack changes: the device links the 2D
+ * components (k_run_links), sums the run lengths per 3D component (k_cc_voxels) and rewrites the labels;
+ * the result is a canonical FLAT version 1 stream (unique list ascending without duplicates and without
+ * labels that nothing carries any more, 0 added when something was removed, keys and stored width from
+ * the new list, is_sorted set) with the input's data width, fortran_order flag, z-index, markov model,
+ * crack codes and slice crcs.  Removed components keep their cracks; ckl_recompress removes those.
+ * n_removed (optional): the 3D components set to 0.  FLAT and pin streams; version 0 and signed streams
+ * are CKL_ERR_ARG; the stream of an empty volume comes back as it is, without a device.  A damaged slice
+ * fails as in ckl_decompress.  *out is released with ckl_free. */
+#define CKL_DUST_BINARY_IMAGE 1
+#define CKL_DUST_INVERT       2
+int ckl_dust(const uint8_t* buf, uint64_t n, uint64_t threshold, int connectivity, int flags, int device,
+             uint8_t** out, uint64_t* out_len, uint64_t* n_removed /* may be NULL */);
+
+/* Host only: the stream `buf` (version 1, unsigned, FLAT or pin labels) with 2D component i of its slices, in
+ * stream order, given the label values[i], at the input's data width (n_values must be the stream's component
+ * count; a value that does not fit the data width is CKL_ERR_ARG).  The result is the canonical FLAT stream
+ * ckl_dust describes: the assembly step of ckl_dust, exported so that it can be tested on its own, and a general
+ * "set every component's label" edit.  The stream of an empty volume comes back as it is.  *out is released
+ * with ckl_free. */
+int ckl_relabel_values(const uint8_t* buf, uint64_t n, const uint64_t* values, uint64_t n_values,
+                       uint8_t** out, uint64_t* out_len);
+
 /* crc32c (Castagnoli; src/crc.hpp:51-57) of a host buffer — exported for tests. */
 uint32_t ckl_crc32c(const uint8_t* data, uint64_t n);
 /* crc32c(A || B) from crc32c(A), crc32c(B) and the byte length of B: lets the ranks of a sharded

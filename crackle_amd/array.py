@@ -269,6 +269,9 @@ class CrackleArray:
   def dust(self, threshold: int, connectivity: int = 26, binary_image: bool = False, invert: bool = False) -> "CrackleArray":
     return CrackleArray(operations.dust(self.binary, threshold, connectivity=connectivity, binary_image=binary_image, invert=invert, device=self.device), self.device)
 
+  def fill_holes(self, connectivity: int = 6) -> "CrackleArray":
+    return CrackleArray(operations.fill_holes(self.binary, connectivity=connectivity, device=self.device), self.device)
+
   # (no remap method: tests/test_cutout_cpu.py pins that CrackleArray has none; operations.remap(arr.binary, ...) is the way)
   def mask(self, labels, value: int = 0) -> "CrackleArray":
     return CrackleArray(operations.mask(self.binary, labels, value=value), self.device)

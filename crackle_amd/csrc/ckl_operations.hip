@@ -1015,7 +1015,8 @@ struct ComponentLinks {
 	uint32_t nc = 0, zero_key = kNoKey, max_runs = 0;
 };
 
-void link_components(ckl_decoder& d, int connectivity, bool binary_image, const char* what, ComponentLinks& L) {
+// mode: what k_run_links unites (LINK_BY_LABEL, LINK_FOREGROUND for dust's binary_image, LINK_BACKGROUND for fill_holes)
+void link_components(ckl_decoder& d, int connectivity, uint32_t mode, const char* what, ComponentLinks& L) {
 	const Header& h = d.head;
 	hipStream_t s = d.stream;
 	decoder_run(d, { Goal::TABLES });
@@ -1034,7 +1035,7 @@ void link_components(ckl_decoder& d, int connectivity, bool binary_image, const 
 	la.zero_key = L.zero_key = d.stats_table[0] == 0 ? 0u : kNoKey;
 	la.sx = h.sx; la.sy = h.sy; la.n_pixels = static_cast<uint32_t>(d.sxy);
 	la.connectivity = static_cast<uint32_t>(connectivity);
-	la.binary = binary_image ? 1u : 0u;
+	la.mode = mode;
 	la.parent = L.parent.p; la.flags = L.flags.p;
 	hipLaunchKernelGGL(k_cc_init, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, L.parent.p, nc);
 	if (L.max_runs) hipLaunchKernelGGL(k_run_links, dim3((L.max_runs + kContactRuns - 1) / kContactRuns, d.nslices), dim3(kContactBlock), 0, s,
@@ -1045,7 +1046,7 @@ void link_components(ckl_decoder& d, int connectivity, bool binary_image, const 
 void decoder_connected_components(ckl_decoder& d, int connectivity, bool want_labels, Components3D& out) {
 	hipStream_t s = d.stream;
 	ComponentLinks L;
-	link_components(d, connectivity, false, "connected_components", L);
+	link_components(d, connectivity, LINK_BY_LABEL, "connected_components", L);
 	const uint32_t nc = L.nc;
 	DevBuf<uint32_t> number, blk;
 	DevBuf<uint64_t> root_label;
@@ -1074,30 +1075,70 @@ void decoder_connected_components(ckl_decoder& d, int connectivity, bool want_la
 	record_span(d);
 }
 
-// dust over the whole stream (ckl_components3d.hpp): the links of connected_components (by label, or
-// binary_image: between any two foreground voxels), the voxels of every set (k_cc_voxels), then the
-// label edit: a component of a set below the threshold (invert: at or above it) gets label 0.  The
-// new unique list is made on the host from one byte per label of the old one; the device packs the
-// keys.  uniq: the new list, ascending; keys: one key per component at key_width bytes.
-struct Dust {
+// The label edit that dust and fill_holes end with (k_edit_mark / k_edit_keys of ckl_components3d.hpp): every
+// component's new label is decided on the device by `edit`; the new unique list is made on the host from one
+// byte per label of the old one, the device packs the keys.  uniq: the new list, ascending; keys: one key per
+// component at key_width bytes; n_changed: the 3D components whose label changed.
+struct LabelEdit {
 	std::vector<uint64_t> uniq;
 	std::vector<uint8_t> keys;
 	int key_width = 1;
-	uint64_t n_removed = 0;
+	uint64_t n_changed = 0;
 };
 
-void decoder_dust(ckl_decoder& d, uint64_t threshold, int connectivity, bool binary_image, bool invert, Dust& out) {
+// (flags: CC_BADKEY of the kernels before is read here; CC_COUNT must be 0 on entry)
+template <typename Edit>
+static void edit_labels(ckl_decoder& d, ComponentLinks& L, const Edit& edit, const char* what, LabelEdit& out) {
 	hipStream_t s = d.stream;
-	ComponentLinks L;
-	link_components(d, connectivity, binary_image, "dust", L);
 	const uint32_t nc = L.nc;
 	const uint32_t n_table = static_cast<uint32_t>(d.stats_table.size());
-	DevBuf<unsigned long long> voxels;
 	DevBuf<uint8_t> used, keys;
 	DevBuf<uint32_t> new_index;
-	voxels.ensure(nc); used.ensure(n_table);
-	CKL_HIP(hipMemsetAsync(voxels.p, 0, nc * sizeof(unsigned long long), s));
+	used.ensure(n_table);
 	CKL_HIP(hipMemsetAsync(used.p, 0, n_table, s));
+	hipLaunchKernelGGL(k_edit_mark<Edit>, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, edit, n_table, used.p, L.flags.p);
+	uint32_t hflags[CC_FLAGS];
+	std::vector<uint8_t> hused(n_table);
+	CKL_HIP(hipMemcpyAsync(hflags, L.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipMemcpyAsync(hused.data(), used.p, n_table, hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	CKL_HIP(hipGetLastError());
+	if (hflags[CC_BADKEY]) throw Error(CKL_ERR_RUNTIME, std::string("crackle_amd: ") + what + ": a component's label is not in the stream's label table");
+	out.n_changed = hflags[CC_COUNT];
+	// the labels still in use, ascending as the table is; 0 in front when a component got it and it was not there
+	const bool add_zero = Edit::kGivesZero && out.n_changed != 0 && !(L.zero_key != kNoKey && hused[L.zero_key]);
+	std::vector<uint32_t> index(n_table, 0);
+	out.uniq.clear();
+	if (add_zero) out.uniq.push_back(0);
+	for (uint32_t k = 0; k < n_table; k++) {
+		if (!hused[k]) continue;
+		index[k] = static_cast<uint32_t>(out.uniq.size());
+		out.uniq.push_back(d.stats_table[k]);
+	}
+	if (out.uniq.empty() || out.uniq.size() > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, std::string("crackle_amd: ") + what + ": the new label list is empty or holds 2^32 labels or more");
+	out.key_width = byte_width(out.uniq.size());
+	upload(new_index, index, s);
+	const uint32_t nq = (nc + 3) / 4;      // four components per thread
+	keys.ensure(16ull * nq);              // the widest keys, padded to a multiple of four
+	hipLaunchKernelGGL(k_edit_keys<Edit>, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, s, edit, n_table, new_index.p, static_cast<uint32_t>(out.uniq.size()), keys.p);
+	out.keys.resize(static_cast<size_t>(nc) * out.key_width);
+	CKL_HIP(hipMemcpyAsync(out.keys.data(), keys.p, out.keys.size(), hipMemcpyDeviceToHost, s));
+	CKL_HIP(hipStreamSynchronize(s));
+	CKL_HIP(hipGetLastError());
+	record_span(d);
+}
+
+// dust over the whole stream (ckl_components3d.hpp): the links of connected_components (by label, or
+// binary_image: between any two foreground voxels), the voxels of every set (k_cc_voxels), then the
+// label edit: a component of a set below the threshold (invert: at or above it) gets label 0.
+void decoder_dust(ckl_decoder& d, uint64_t threshold, int connectivity, bool binary_image, bool invert, LabelEdit& out) {
+	hipStream_t s = d.stream;
+	ComponentLinks L;
+	link_components(d, connectivity, binary_image ? LINK_FOREGROUND : LINK_BY_LABEL, "dust", L);
+	const uint32_t nc = L.nc;
+	DevBuf<unsigned long long> voxels;
+	voxels.ensure(nc);
+	CKL_HIP(hipMemsetAsync(voxels.p, 0, nc * sizeof(unsigned long long), s));
 	VoxelArgs va;
 	va.comp_key = L.comp_key.p; va.zero_key = L.zero_key;
 	va.n_pixels = static_cast<uint32_t>(d.sxy);
@@ -1108,36 +1149,35 @@ void decoder_dust(ckl_decoder& d, uint64_t threshold, int connectivity, bool bin
 	da.root = L.root.p; da.comp_key = L.comp_key.p; da.voxels = voxels.p;
 	da.zero_key = L.zero_key; da.n = nc;
 	da.threshold = threshold; da.invert = invert ? 1u : 0u;
-	hipLaunchKernelGGL(k_dust_mark, dim3((nc + kBlock - 1) / kBlock), dim3(kBlock), 0, s, da, n_table, used.p, L.flags.p);
-	uint32_t hflags[CC_FLAGS];
-	std::vector<uint8_t> hused(n_table);
-	CKL_HIP(hipMemcpyAsync(hflags, L.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipMemcpyAsync(hused.data(), used.p, n_table, hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipStreamSynchronize(s));
-	CKL_HIP(hipGetLastError());
-	if (hflags[CC_BADKEY]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: dust: a component's label is not in the stream's label table");
-	out.n_removed = hflags[CC_COUNT];
-	// the labels still in use, ascending as the table is; 0 in front when something was removed and it was not there
-	const bool add_zero = out.n_removed != 0 && !(L.zero_key != kNoKey && hused[L.zero_key]);
-	std::vector<uint32_t> index(n_table, 0);
-	out.uniq.clear();
-	if (add_zero) out.uniq.push_back(0);
-	for (uint32_t k = 0; k < n_table; k++) {
-		if (!hused[k]) continue;
-		index[k] = static_cast<uint32_t>(out.uniq.size());
-		out.uniq.push_back(d.stats_table[k]);
+	edit_labels(d, L, da, "dust", out);
+}
+
+// fill_holes over the whole stream (ckl_components3d.hpp): the links of label 0's components at the wanted
+// connectivity, one state word per background set from the face neighbours of its runs (k_hole_scan), then the
+// label edit: a component of a set that lies on no face of the volume and saw exactly one label gets that label.
+void decoder_fill_holes(ckl_decoder& d, int connectivity, LabelEdit& out) {
+	hipStream_t s = d.stream;
+	const Header& h = d.head;
+	ComponentLinks L;
+	link_components(d, connectivity, LINK_BACKGROUND, "fill_holes", L);
+	if (d.nslices != h.sz) throw Error(CKL_ERR_RUNTIME, "crackle_amd: fill_holes: the decoder does not cover the whole volume");
+	if (d.stats_table.size() >= HOLE_MANY - 1u) throw Error(CKL_ERR_RUNTIME, "crackle_amd: fill_holes: 2^32 - 3 labels or more");
+	const uint32_t nc = L.nc;
+	DevBuf<uint32_t> state;
+	state.ensure(nc);
+	CKL_HIP(hipMemsetAsync(state.p, 0, nc * sizeof(uint32_t), s));
+	if (L.max_runs && L.zero_key != kNoKey) {
+		HoleArgs ha;
+		ha.comp_key = L.comp_key.p; ha.zero_key = L.zero_key;
+		ha.sx = h.sx; ha.sy = h.sy; ha.n_pixels = static_cast<uint32_t>(d.sxy); ha.nslices = d.nslices;
+		ha.root = L.root.p; ha.state = state.p; ha.flags = L.flags.p;
+		hipLaunchKernelGGL(k_hole_scan, dim3((L.max_runs + kContactRuns - 1) / kContactRuns, d.nslices), dim3(kContactBlock), 0, s,
+			run_geom(d), run_arrays(d), d.d_comp_off.p, d.d_ncomp_expect.p, ha);
 	}
-	if (out.uniq.empty() || out.uniq.size() > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: dust: the new label list is empty or holds 2^32 labels or more");
-	out.key_width = byte_width(out.uniq.size());
-	upload(new_index, index, s);
-	const uint32_t nq = (nc + 3) / 4;      // four components per thread
-	keys.ensure(16ull * nq);              // the widest keys, padded to a multiple of four
-	hipLaunchKernelGGL(k_dust_keys, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, s, da, n_table, new_index.p, static_cast<uint32_t>(out.uniq.size()), keys.p);
-	out.keys.resize(static_cast<size_t>(nc) * out.key_width);
-	CKL_HIP(hipMemcpyAsync(out.keys.data(), keys.p, out.keys.size(), hipMemcpyDeviceToHost, s));
-	CKL_HIP(hipStreamSynchronize(s));
-	CKL_HIP(hipGetLastError());
-	record_span(d);
+	FillArgs fa;
+	fa.root = L.root.p; fa.comp_key = L.comp_key.p; fa.state = state.p;
+	fa.zero_key = L.zero_key; fa.n = nc;
+	edit_labels(d, L, fa, "fill_holes", out);
 }
 
 // operations::point_cloud (src/operations.hpp:183-262): contours of every component of the decoder's
@@ -1619,7 +1659,7 @@ int ckl_dust(
 		const Header h = Header::parse(buf, n);
 		if (h.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: dust: version 0 streams have no crack crcs to carry over: recompress() first");
 		if (h.is_signed) throw Error(CKL_ERR_ARG, "crackle_amd: dust: signed streams are not supported");
-		Dust du;
+		LabelEdit du;
 		if (h.voxels() != 0) {      // (an empty volume comes back as it is, from the host alone)
 			DecoderPtr d;
 			const int rc = open_decoder(buf, n, 0, -1, device, d);
@@ -1628,7 +1668,33 @@ int ckl_dust(
 			decoder_dust(*d, threshold, connectivity, (flags & CKL_DUST_BINARY_IMAGE) != 0, (flags & CKL_DUST_INVERT) != 0, du);
 		}
 		*out = relabel_stream_keep_width(buf, n, du.uniq, du.keys.data(), du.key_width, du.keys.size() / du.key_width, out_len);
-		if (n_removed) *n_removed = du.n_removed;
+		if (n_removed) *n_removed = du.n_changed;
+		return CKL_OK;
+	});
+}
+
+int ckl_fill_holes(
+	const uint8_t* buf, uint64_t n, int connectivity, int device,
+	uint8_t** out, uint64_t* out_len, uint64_t* n_filled
+) {
+	return guard([&]() -> int {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		*out = nullptr; *out_len = 0;
+		if (n_filled) *n_filled = 0;
+		if (connectivity != 6 && connectivity != 18 && connectivity != 26) throw Error(CKL_ERR_ARG, "crackle_amd: fill_holes: connectivity must be 6, 18 or 26");
+		const Header h = Header::parse(buf, n);
+		if (h.format_version != 1) throw Error(CKL_ERR_ARG, "crackle_amd: fill_holes: version 0 streams have no crack crcs to carry over: recompress() first");
+		if (h.is_signed) throw Error(CKL_ERR_ARG, "crackle_amd: fill_holes: signed streams are not supported");
+		LabelEdit fh;
+		if (h.voxels() != 0) {      // (an empty volume comes back as it is, from the host alone)
+			DecoderPtr d;
+			const int rc = open_decoder(buf, n, 0, -1, device, d);
+			if (rc != CKL_OK) return rc;
+			enter(d.get());
+			decoder_fill_holes(*d, connectivity, fh);
+		}
+		*out = relabel_stream_keep_width(buf, n, fh.uniq, fh.keys.data(), fh.key_width, fh.keys.size() / fh.key_width, out_len);
+		if (n_filled) *n_filled = fh.n_changed;
 		return CKL_OK;
 	});
 }

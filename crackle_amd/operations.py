@@ -428,6 +428,56 @@ def dust(
   return (result, int(removed.value)) if return_removed else result
 
 
+def fill_holes(binary: bytes, connectivity: int = 6, return_filled: bool = False, device: int = 0) -> Union[bytes, Tuple[bytes, int]]:
+  """The stream with its enclosed background voids filled (the fill_holes of fill_voids and fastmorph; the
+  reference has none).  With return_filled: also the number of holes filled.
+
+  A hole is a maximal set of voxels with label 0 joined by 6-, 18- or 26-neighbour steps: `connectivity` is the
+  background's, and at 6 the surrounding object only needs to be 26-connected around the hole.  A hole is filled
+  with label L when both hold: (1) none of its voxels lies on a face of the volume (x = 0, x = sx - 1, y = 0,
+  y = sy - 1, z = 0 or z = sz - 1); (2) every face neighbour of its voxels that is not itself in the hole carries
+  the same label L, where only the 6 face neighbours count, whatever `connectivity` is.  Every other hole stays 0:
+  one on the border, and one that touches two or more labels by faces.  Nothing else changes.  So a volume with
+  sz = 1 has no fillable hole, diagonal contact with a second label does not prevent filling, and, equality being
+  by label, background components separated only by "false boundaries" (the output of dust() or mask() before
+  recompress()) are one hole.
+
+  Nothing is decoded to voxels and no crack changes: the device links label 0's 2D components as
+  connected_components links the others, scans the face neighbours of every background run into one state word
+  per hole and rewrites the labels (ckl_fill_holes).  The result is a canonical FLAT stream, format version 1, as
+  dust() documents its own: the unique list ascending without duplicates (label 0 leaves it when every hole was
+  filled), the keys at the width of the new count, the stored width from the largest remaining label, is_sorted
+  set.  Data width and fortran_order flag are the input's; z-index, markov model, crack codes and slice crcs are
+  the input's bytes.  If nothing is filled and the input is a FLAT version 1 stream from compress(), the output is
+  the input.  Filled holes keep their cracks ("false boundaries") until recompress().
+
+  FLAT and pin label streams are accepted (a pin stream comes back FLAT).  A connectivity other than 6, 18 or 26
+  raises ValueError, format version 0 ValueError, signed streams TypeError.  The stream of an empty volume is
+  returned as it is, without a device.  A damaged slice raises what decompress raises for it.
+
+  Not done: filling holes with more than one surrounding label (an `ambiguous=` policy), a size limit on holes,
+  per-label filling that swallows enclosed foreign labels (fastmorph's remove_enclosed), z-ranges, a sharded
+  version."""
+  from .codec import _raise
+  if connectivity not in (6, 18, 26):
+    raise ValueError(f"fill_holes: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  b = bytes(binary)
+  head = header(b)
+  if head.format_version == 0:
+    raise ValueError("fill_holes: format version 0 streams have no crack crcs to carry over; recompress() first.")
+  if head.signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  if head.voxels() == 0:
+    return (b, 0) if return_filled else b
+  out, n, filled = C.c_void_p(), C.c_uint64(), C.c_uint64()
+  rc = _lib.lib().ckl_fill_holes(b, len(b), int(connectivity), int(device), C.byref(out), C.byref(n),
+                                 C.byref(filled) if return_filled else None)
+  if rc != _lib.CKL_OK:
+    _raise(rc)
+  result = _take(out, n)
+  return (result, int(filled.value)) if return_filled else result
+
+
 # ---- label edits: remap / mask / mask_except on the host, recompress on the device ------------------------------------
 def _byte_width(x: int) -> int:
   return 1 if x <= 0xFF else 2 if x <= 0xFFFF else 4 if x <= 0xFFFFFFFF else 8

@@ -546,6 +546,21 @@ int ckl_relabel_components(const uint8_t* buf, uint64_t n, const uint64_t* new_i
 int ckl_dust(const uint8_t* buf, uint64_t n, uint64_t threshold, int connectivity, int flags, int device,
              uint8_t** out, uint64_t* out_len, uint64_t* n_removed /* may be NULL */);
 
+/* Fills the enclosed background voids of a stream (the fill_holes of fill_voids / fastmorph; the reference has no
+ * such function).  A hole is a maximal set of voxels with label 0 joined by 6-, 18- or 26-neighbour steps
+ * (`connectivity`: the background's).  It is filled with label L when none of its voxels lies on a face of the
+ * volume and every face neighbour (the 6 face neighbours, whatever `connectivity` is) of its voxels that is not
+ * itself in the hole carries the same label L; every other hole stays 0.  No voxel is decoded and no crack
+ * changes: the device links label 0's 2D components (k_run_links), scans the face neighbours of their runs
+ * (k_hole_scan) and rewrites the labels; the result is the canonical FLAT version 1 stream ckl_dust describes
+ * (label 0 leaves the unique list when every hole was filled) with the input's data width, fortran_order
+ * flag, z-index, markov model, crack codes and slice crcs.  Filled holes keep their cracks; ckl_recompress
+ * removes those.  n_filled (optional): the holes filled.  FLAT and pin streams; a connectivity other than
+ * 6, 18 or 26, version 0 and signed streams are CKL_ERR_ARG; the stream of an empty volume comes back as it
+ * is, without a device.  A damaged slice fails as in ckl_decompress.  *out is released with ckl_free. */
+int ckl_fill_holes(const uint8_t* buf, uint64_t n, int connectivity, int device,
+                   uint8_t** out, uint64_t* out_len, uint64_t* n_filled /* may be NULL */);
+
 /* Host only: the stream `buf` (version 1, unsigned, FLAT or pin labels) with 2D component i of its slices, in
  * stream order, given the label values[i], at the input's data width (n_values must be the stream's component
  * count; a value that does not fit the data width is CKL_ERR_ARG).  The result is the canonical FLAT stream

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libcrackle_amd_tuning.so" if os.environ.get("CKL_
 CKL_OK, CKL_ERR_FORMAT, CKL_ERR_RUNTIME, CKL_ERR_ARG, CKL_ERR_NO_DEVICE, CKL_ERR_CRC = range(6)
 MEM_HOST, MEM_DEVICE = 0, 1
 CKL_DUST_BINARY_IMAGE, CKL_DUST_INVERT = 1, 2
+CKL_ERODE_KEEP_BORDER = 1
 
 
 class HeaderInfo(C.Structure):
@@ -119,6 +120,7 @@ EXPORTS = {
     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_reencode_markov": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_recompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+  "ckl_erode": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_decoder_crack_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
   "ckl_zsplit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_encoder_defer_codes": (C.c_int, [C.c_void_p, C.c_int]),

@@ -282,6 +282,9 @@ class CrackleArray:
   def recompress(self, markov_model_order: Optional[int] = None) -> "CrackleArray":
     return CrackleArray(operations.recompress(self.binary, markov_model_order=markov_model_order, device=self.device), self.device)
 
+  def erode(self, connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":
+    return CrackleArray(operations.erode(self.binary, connectivity=connectivity, erode_border=erode_border, device=self.device), self.device)
+
   def voxel_connectivity_graph(self, connectivity: int = 4) -> np.ndarray:
     return codec.voxel_connectivity_graph(self.binary, connectivity, device=self.device)
 

@@ -17,6 +17,7 @@
 #include "ckl_strips.hpp"
 #include "ckl_trail.hpp"
 #include "ckl_recompress.hpp"
+#include "ckl_erode.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -2339,7 +2340,12 @@ void encode_typed(
 // The bytes are those of compress(decompress(stream), markov_model_order): the planes, max label and pixel pairs are
 // functions of the labels alone, and everything behind them is the encoder's own.
 void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_signed);
-void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, uint8_t** out, uint64_t* out_len) {
+// erode (ckl_erode: the same road with another volume at its end): the planes, counts, pairs and maximum are those of the
+// eroded labels (ckl_erode.hpp) and the label stage reads the keep plane beside the tables; nullptr: recompress
+struct ErodeSpec { int connectivity; bool keep_border; };
+void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, uint8_t** out, uint64_t* out_len, const ErodeSpec* erode = nullptr) {
+	if (erode && erode->connectivity != 6 && erode->connectivity != 18 && erode->connectivity != 26)
+		throw Error(CKL_ERR_ARG, "crackle_amd: erode: connectivity must be 6, 18 or 26. Got: " + std::to_string(erode->connectivity));
 	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
 	const Header head = Header::parse(buf, n);
 	if (head.is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
@@ -2389,11 +2395,26 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, ui
 	CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, 3 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
 	CKL_HIP(hipMemsetAsync(e.d_stats.p, 0, sizeof(unsigned long long), s));
 	CKL_HIP(hipEventRecord(e.evd0, s));
-	hipLaunchKernelGGL(k_label_planes_from_runs, dim3(static_cast<uint32_t>((e.plane_words + kBlock - 1) / kBlock), ns), dim3(kBlock), 0, s,
-		src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
-	CKL_HIP(hipEventRecord(e.evd1, s));
-	hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, s,
-		d.d_label_map.p, d.total_comp, e.d_stats.p);
+	const dim3 word_grid(static_cast<uint32_t>((e.plane_words + kBlock - 1) / kBlock), ns);
+	if (erode) {
+		const size_t pw = e.plane_words * ns;
+		e.d_erode_bits.ensure(4 * pw);      // P | C | D | K
+		d.d_run_label.ensure(d.rtot);       // (PAINT's scratch of the decode session: one label per run, at the runs' own bases)
+		uint32_t *plane_p = e.d_erode_bits.p, *plane_c = plane_p + pw, *plane_d = plane_c + pw, *keep = plane_d + pw;
+		const ErodeArgs ea = { static_cast<uint32_t>(erode->connectivity), erode->keep_border ? 1u : 0u, ns };
+		hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((d.max_rcap + kBlock - 1) / kBlock + 1, 256), ns), dim3(kBlock), 0, s, src, d.d_run_label.p);
+		hipLaunchKernelGGL(k_erode_terms, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, ea, plane_p, plane_c, plane_d);
+		hipLaunchKernelGGL(k_erode_keep, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, ea, plane_p, plane_c, plane_d, keep, e.d_stats.p);
+		hipLaunchKernelGGL(k_erode_planes, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, keep, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
+		CKL_HIP(hipEventRecord(e.evd1, s));
+		src.keep = keep;
+	}
+	else {
+		hipLaunchKernelGGL(k_label_planes_from_runs, word_grid, dim3(kBlock), 0, s, src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
+		CKL_HIP(hipEventRecord(e.evd1, s));
+		hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, s,
+			d.d_label_map.p, d.total_comp, e.d_stats.p);
+	}
 	const std::vector<uint32_t> c = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), s);
 	const std::vector<unsigned long long> mx = download(e.d_stats.p, 1, s);
 	float ms_kernel = 0.f;
@@ -2427,7 +2448,9 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, ui
 			else if (name == "assembly" || name == "codes_d2h") assembly += m.second;
 			else labels += m.second;      // f:*, flat, l:*, label_table, labels_d2h: the label side, on the host under the crack trail
 		}
-		fprintf(stderr, "[ckl recompress host ms] tables=%.2f label_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_label_planes_from_runs_device=%.3f\n",
+		if (erode) fprintf(stderr, "[ckl erode host ms] tables=%.2f keep_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_erode_device=%.3f\n",
+			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
+		else fprintf(stderr, "[ckl recompress host ms] tables=%.2f label_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_label_planes_from_runs_device=%.3f\n",
 			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
 	}
 }
@@ -2608,6 +2631,15 @@ int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int d
 	return guard([&] {
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		recompress(buf, n, markov_model_order, device, out, out_len);
+	});
+}
+
+int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		if (flags & ~CKL_ERODE_KEEP_BORDER) throw Error(CKL_ERR_ARG, "crackle_amd: erode: unknown flags");
+		const ErodeSpec spec = { connectivity, (flags & CKL_ERODE_KEEP_BORDER) != 0 };
+		recompress(buf, n, markov_model_order, device, out, out_len, &spec);
 	});
 }
 

@@ -78,6 +78,7 @@ struct ckl_encoder {
 	// ckl_recompress: there is no volume.  The planes stand in d_planes (planes_stats, count_v / count_h as for cached
 	// planes) and the label stage takes every component's label from these run tables of a decode session (ckl_recompress.hpp)
 	const ckl::dev::RunLabels* label_src = nullptr;
+	DevBuf<uint32_t> d_erode_bits;     // ckl_erode: the planes P | C | D | K of ckl_erode.hpp, [nslices][plane_words] each; K lives through the label stage
 	std::vector<std::pair<const char*, double>> host_marks;      // ... and the host timer's marks of that run, for recompress' own line
 	VolumeStats planes_stats;          // max / pairs of the volume the cached planes were built from
 	int64_t planes_dims[3] = { 0, 0, 0 };

@@ -24,6 +24,7 @@ struct RunLabels {
 	const uint64_t* comp_off;       // per slice base into label_map
 	const uint32_t* ncomp;          // [nslices] components as the label section states them
 	const uint64_t* label_map;      // component -> label
+	const uint32_t* keep = nullptr; // ckl_erode.hpp: [nslices][plane_words], a pixel whose bit is 0 carries label 0 (nullptr: every pixel keeps its label)
 
 	// label of run `run` of slice zi; everything read from the tables is clamped as k_paint_window clamps it
 	__device__ __forceinline__ uint64_t label_of(uint32_t zi, uint32_t run) const {
@@ -148,7 +149,9 @@ __global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
 	uint32_t pix = slots ? static_cast<uint32_t>(slots[static_cast<uint64_t>(zi) * slot_cap + c]) : comp_pix[rbase_enc[zi] + c];
 	pix = pix < n_pixels ? pix : n_pixels - 1u;
 	const uint32_t y = pix / t.g.sx;
-	mapping[comp_off[zi] + c] = t.label_of(zi, t.run_at(zi, pix - y * t.g.sx, y));
+	const uint32_t x = pix - y * t.g.sx;
+	const bool kept = !t.keep || ((t.keep[zi * t.g.plane_words + static_cast<uint64_t>(y) * t.g.row_words + (x >> 5)] >> (x & 31u)) & 1u);
+	mapping[comp_off[zi] + c] = kept ? t.label_of(zi, t.run_at(zi, x, y)) : 0ull;
 }
 
 }  // namespace dev

@@ -622,3 +622,42 @@ def recompress(
   if rc != _lib.CKL_OK:
     _raise(rc)
   return _take(out, n)
+
+
+def erode(
+  binary: bytes, connectivity: int = 26, erode_border: bool = True,
+  markov_model_order: Optional[int] = None, device: int = 0,
+) -> bytes:
+  """compress(eroded, markov_model_order=m), byte for byte, where eroded is the stream's volume with every label
+  peeled back by one voxel (fastmorph's erode; the reference has none), without the voxels.
+
+  A voxel keeps its label L != 0 iff every neighbour of the structuring element carries L; otherwise it becomes 0.
+  The element is the 6, 18 or 26 offsets (dx, dy, dz) in {-1, 0, 1}^3 with 0 < |dx| + |dy| + |dz| <= 1, 2, 3.
+  Equality is by label: the false boundaries that remap, mask, dust or fill_holes leave erode nothing.  With
+  erode_border a neighbour outside the volume counts as different (every voxel on a face of the volume goes);
+  without it such neighbours are ignored, which for these elements is edge replication.  One iteration per call.
+
+  m is the input's order unless markov_model_order is given.  The output has FLAT labels, format version 1,
+  whatever the input had (FLAT, pins, version 0), the input's data width and fortran_order flag, and the stored
+  width of the largest label that survives; when nothing survives it is the stream of an all-zero volume.
+
+  On the device the decoder runs up to its run tables; the keep bit of every pixel is worked out from the runs
+  (ckl_erode.hpp), the encoder's planes are the XOR of that bit plane with itself shifted by one pixel and by one
+  row, and the encoder's crack and label stages follow as for recompress (ckl_erode).  Signed streams raise
+  TypeError, a bad connectivity or a negative order ValueError; a damaged slice raises what decompress raises for
+  it; the stream of an empty volume comes back as recompress returns it, without a device."""
+  from .codec import _raise
+  if connectivity not in (6, 18, 26):
+    raise ValueError(f"erode: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  b = bytes(binary)
+  if header(b).signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  order = -1 if markov_model_order is None else int(markov_model_order)
+  if markov_model_order is not None and order < 0:
+    raise ValueError(f"erode: markov_model_order must not be negative. Got: {order}")
+  flags = 0 if erode_border else _lib.CKL_ERODE_KEEP_BORDER
+  out, n = C.c_void_p(), C.c_uint64()
+  rc = _lib.lib().ckl_erode(b, len(b), int(connectivity), flags, order, int(device), C.byref(out), C.byref(n))
+  if rc != _lib.CKL_OK:
+    _raise(rc)
+  return _take(out, n)

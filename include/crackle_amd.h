@@ -501,6 +501,24 @@ int ckl_reencode_markov(const uint8_t* buf, uint64_t n, int markov_model_order, 
  * streams are CKL_ERR_ARG.  *out is released with ckl_free. */
 int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len);
 
+/* Morphological erosion of a stream's labels by one voxel (fastmorph's erode; the reference has no such
+ * function): the stream that ckl_compress gives for the eroded volume, written as ckl_recompress writes its own
+ * (FLAT labels, format version 1, markov_model_order < 0: keep the input's, the input's data width and
+ * fortran_order flag, the stored width of the largest surviving label).  A voxel keeps its label L != 0 iff
+ * every neighbour of the structuring element carries L, and becomes 0 otherwise; the element is the 6, 18 or 26
+ * (`connectivity`) offsets of {-1, 0, 1}^3 with 0 < |dx| + |dy| + |dz| <= 1, 2, 3.  Labels are compared, not
+ * runs or components: cracks between components that share a label erode nothing.  A neighbour outside the
+ * volume counts as different, so every voxel on a face of the volume goes; with CKL_ERODE_KEEP_BORDER (the only
+ * flag) such neighbours are ignored.  No voxel is decoded: the decoder runs up to its run tables, the keep bit K
+ * of every pixel is worked out from the runs (k_erode_run_labels, k_erode_terms, k_erode_keep), the encoder's
+ * planes are K ^ K(x - 1) and K ^ K(y - 1) (k_erode_planes), and the encoder's crack and label stages follow,
+ * the label stage reading K beside the tables.  FLAT, pin and version 0 streams; signed streams, another
+ * connectivity and unknown flags are CKL_ERR_ARG; the stream of an empty volume comes back as ckl_recompress
+ * returns it, without a device.  A damaged slice fails as in ckl_decompress.  *out is released with ckl_free. */
+#define CKL_ERODE_KEEP_BORDER 1
+int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device,
+              uint8_t** out, uint64_t* out_len);
+
 /* Native form of crackle.operations.zsplit's range helper (crackle/operations.py:550-623):
  * the stream of slices [z_start, z_end) of a FLAT stream, without decoding (host only).
  * *out is released with ckl_free. */

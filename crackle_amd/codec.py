@@ -65,13 +65,16 @@ def labels(binary: bytes) -> np.ndarray:
 
 
 def contains(binary: bytes, label: int) -> bool:
-  """codec.py:98-132 (sorted search on the unique label list)."""
+  """codec.py:98-132: a sorted search on the unique label list, or, where the header's is_sorted flag is cleared
+  (the reference's remap leaves such lists), a linear one."""
   head = header(binary)
   if head.voxels() == 0:
     return False
   u = labels(binary)
   if label < 0 or label > np.iinfo(u.dtype).max:
     return False
+  if not head.is_sorted:
+    return bool((u == u.dtype.type(label)).any())
   i = np.searchsorted(u, u.dtype.type(label))
   return bool(i < u.size and u[i] == label)
 
@@ -155,7 +158,9 @@ def decompress_range(
   if sx * sy * sz == 0:
     out = np.zeros((0,), dtype=head.dtype)
   elif label is not None and not contains(binary, label):
-    out = np.zeros(shape, order=order, dtype=head.dtype)
+    # one byte per voxel, as the device writes a binary image (the reference makes these zeros at the stream's data
+    # width, and its view(bool) below then raises for every width but 1)
+    out = np.zeros(shape, order=order, dtype=np.uint8)
   elif label is None and num_labels(binary) == 1:
     single = labels(binary)[0]
     out = np.zeros(shape, order=order, dtype=head.dtype) if single == 0 else np.full(shape, single, order=order, dtype=head.dtype)
@@ -381,8 +386,11 @@ def check(binary: bytes, device: int = 0) -> dict:
     if stored != int(L.ckl_crc32c(binary[hb:hb + 4 * head.sz], 4 * head.sz)):
       sections["crack_index"] = False
       return sections
-  # the reference's offsets leave the markov model out here (codec.py:277-281); kept
-  if hb + gib + head.num_label_bytes + int(zidx.astype(np.uint64).sum()) >= len(binary):
+  # the reference's offsets leave the markov model out here (codec.py:277-281); kept.  Its test is >= for every
+  # version (codec.py:926), which calls an intact version 0 stream of markov order 0 damaged: nothing follows the
+  # crack codes there, so they end exactly at the end of the stream
+  end = hb + gib + head.num_label_bytes + int(zidx.astype(np.uint64).sum())
+  if end > len(binary) or (end == len(binary) and head.format_version > 0):
     sections["crack_index"] = False
     return sections
   sections["crack_index"] = True

@@ -10,7 +10,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _lib
-from .codec import contains, header, labels, num_labels
+from .codec import contains, header, labels
 
 
 def _take(out: C.c_void_p, n: C.c_uint64) -> bytes:
@@ -23,7 +23,10 @@ def _take(out: C.c_void_p, n: C.c_uint64) -> bytes:
 def zstack(images: Sequence[bytes]) -> bytes:
   """Concatenates the streams of consecutive z-slabs into the stream of the whole volume
   (crackle/operations.py:424-548); byte-identical to compress() of the whole when the slabs
-  agree on the crack format (automated_test.py:468-487)."""
+  agree on the crack format (automated_test.py:468-487).  The result's label list is the sorted union of the slabs'
+  lists, which may be out of order or hold duplicates.  FLAT label streams of format version 1 only: a pin label
+  stream or a version 0 stream raises ValueError (recompress() gives a FLAT version 1 stream first), and so do slabs
+  that disagree on shape, dtype, crack format or markov order, as in the reference ("All crack formats must match.")."""
   bufs = [bytes(b) for b in images]
   if not bufs:
     raise ValueError("zstack needs at least one stream")
@@ -56,7 +59,8 @@ def _zrange(binary: bytes, z_start: int, z_end: int) -> bytes:
 
 def zsplit(binary: bytes, z: int) -> Tuple[bytes, bytes, bytes]:
   """(before, middle, after) streams around slice z (crackle/operations.py:626-647); empty
-  ranges come back as b''."""
+  ranges come back as b''.  Each part keeps the labels its slices use, in the order of the input's list.  Pin label
+  streams and format version 0 raise ValueError, as for zstack."""
   head = header(binary)
   if z < 0 or z >= head.sz:
     raise ValueError(f"{z} is outside the range 0 to {head.sz}.")
@@ -73,21 +77,30 @@ def zshatter(binary: bytes) -> List[bytes]:
 
 
 def array_equal(binary1: bytes, binary2: bytes, parallel: int = 0, device: int = 0) -> bool:
-  """Do the two streams hold the same array, whatever their encoding (crackle/operations.py:966-994:
-  shapes, number of labels and label sets are compared on the host, then
-  fastcrackle.array_equal = src/operations.hpp:1039-1184 -> ckl_array_equal)."""
+  """Do the two streams hold the same array, whatever their encoding: dtype, FLAT or pin labels, format version,
+  markov order, memory order, label list in or out of order or with duplicates, false boundaries.
+
+  Shapes and label sets are compared on the host, as the reference compares them first (crackle/operations.py:966-994;
+  it compares the lists as stored, which calls a remapped stream unequal to its own canonical form).  The voxels are
+  then compared on the device through the contingency table of the two streams (ckl_overlaps): the arrays are equal
+  iff no voxel pairs two different labels.  The reference's fastcrackle.array_equal (src/operations.hpp:1039-1184,
+  kept as ckl_array_equal) compares the component counts of the slices and reads both streams through the first
+  one's component -> label table, so it calls a stream with false boundaries unequal to its re-encoding and cannot
+  see labels exchanged between components; it still answers for streams without voxels."""
   b1, b2 = bytes(binary1), bytes(binary2)
   h1, h2 = header(b1), header(b2)
   if h1.sx != h2.sx or h1.sy != h2.sy or h1.sz != h2.sz:
     return False
-  if num_labels(b1) != num_labels(b2):
+  u1, u2 = np.unique(labels(b1)), np.unique(labels(b2))
+  if u1.size != u2.size or np.any(u1 != u2):
     return False
-  if np.any(labels(b1) != labels(b2)):
-    return False
-  eq = C.c_int(0)
-  if _lib.lib().ckl_array_equal(b1, len(b1), b2, len(b2), int(device), C.byref(eq)) != _lib.CKL_OK:
-    raise RuntimeError(_lib.last_error())
-  return bool(eq.value)
+  if h1.voxels() == 0:
+    eq = C.c_int(0)
+    if _lib.lib().ckl_array_equal(b1, len(b1), b2, len(b2), int(device), C.byref(eq)) != _lib.CKL_OK:
+      raise RuntimeError(_lib.last_error())
+    return bool(eq.value)
+  pairs, _ = _overlap_counts(b1, b2, 0, -1, device)
+  return bool((pairs[:, 0] == pairs[:, 1]).all())
 
 
 def _mode_pooling_slices(binary: bytes, z_start: int = 0, z_end: int = -1, device: int = 0) -> List[bytes]:
@@ -114,7 +127,9 @@ def _mode_pooling_slices(binary: bytes, z_start: int = 0, z_end: int = -1, devic
 
 def mode_pooling_2x2x1(binary: bytes, parallel: int = 0, device: int = 0) -> bytes:
   """Downsamples a segmentation 2 x 2 x 1 by the reference's pooling rule
-  (crackle/operations.py:1023-1026: the per-slice streams of fastcrackle.mode_pooling_2x2x1, stacked)."""
+  (crackle/operations.py:1023-1026: the per-slice streams of fastcrackle.mode_pooling_2x2x1, stacked).  Every pooled
+  slice is compressed on its own and picks its own crack format; where the slices do not all pick the same one
+  (noise of two or three labels does that) zstack cannot join them and raises ValueError, as the reference does."""
   return zstack(_mode_pooling_slices(binary, 0, -1, device))
 
 

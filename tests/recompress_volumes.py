@@ -77,6 +77,39 @@ def as_signed(binary):
   return bytes(head) + bytes([crc]) + bytes(binary[29:])
 
 
+def _crc8(data):
+  crc = 0xFF
+  for byte in data:
+    crc ^= byte
+    for _ in range(8):
+      crc = (crc >> 1) ^ 0xE7 if crc & 1 else crc >> 1
+  return crc
+
+
+def permuted_stream(binary, fn=lambda v: (7 * v) % 41):
+  """What the reference's remap writes for a flat stream (crackle/codec.py:747-776): the unique list rewritten v -> fn(v)
+  in place, in whatever order that leaves it and with the duplicates it makes, bit 13 of the format field ("not
+  sorted") set, the header's crc8 and the label crc32c redone.  The default is injective on 0 .. 40, keeps 0 and is
+  not monotone."""
+  import crackle_amd
+  from crackle_amd import _lib, codec
+  b = bytearray(binary)
+  head = crackle_amd.header(bytes(b))
+  assert head.format_version == 1 and head.label_format == 0
+  n, off = codec._label_section(bytes(b), head)
+  uniq = np.frombuffer(bytes(b), dtype=head.stored_dtype, offset=off, count=n)
+  new = np.array([fn(int(v)) for v in uniq.tolist()], dtype=np.uint64)
+  assert int(new.max()) <= np.iinfo(head.stored_dtype).max, "a new value does not fit the stored width"
+  b[off:off + uniq.nbytes] = new.astype(head.stored_dtype).tobytes()
+  b[5:7] = (int.from_bytes(b[5:7], "little") | (1 << 13)).to_bytes(2, "little")
+  b[28] = _crc8(b[5:28])
+  start = head.header_bytes + head.grid_index_bytes
+  crc = _lib.lib().ckl_crc32c(bytes(b[start:start + head.num_label_bytes]), head.num_label_bytes)
+  at = len(b) - (head.sz * 4 + 4)
+  b[at:at + 4] = int(crc).to_bytes(4, "little")
+  return bytes(b)
+
+
 def floordiv_stream(binary, divisor=2):
   """What the reference's floordiv_scalar writes for a flat stream (as tests/test_gpu_connected_components.py builds
   its merged input): the unique list rewritten v // divisor in place, duplicates and all, the label crc fixed."""

@@ -285,6 +285,15 @@ class CrackleArray:
   def erode(self, connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":
     return CrackleArray(operations.erode(self.binary, connectivity=connectivity, erode_border=erode_border, device=self.device), self.device)
 
+  def dilate(self, connectivity: int = 26) -> "CrackleArray":
+    return CrackleArray(operations.dilate(self.binary, connectivity=connectivity, device=self.device), self.device)
+
+  def opening(self, connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":
+    return CrackleArray(operations.opening(self.binary, connectivity=connectivity, erode_border=erode_border, device=self.device), self.device)
+
+  def closing(self, connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":
+    return CrackleArray(operations.closing(self.binary, connectivity=connectivity, erode_border=erode_border, device=self.device), self.device)
+
   def voxel_connectivity_graph(self, connectivity: int = 4) -> np.ndarray:
     return codec.voxel_connectivity_graph(self.binary, connectivity, device=self.device)
 

@@ -18,6 +18,7 @@
 #include "ckl_trail.hpp"
 #include "ckl_recompress.hpp"
 #include "ckl_erode.hpp"
+#include "ckl_dilate.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -2343,9 +2344,17 @@ void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_sign
 // erode (ckl_erode: the same road with another volume at its end): the planes, counts, pairs and maximum are those of the
 // eroded labels (ckl_erode.hpp) and the label stage reads the keep plane beside the tables; nullptr: recompress
 struct ErodeSpec { int connectivity; bool keep_border; };
-void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, uint8_t** out, uint64_t* out_len, const ErodeSpec* erode = nullptr) {
+// dilate (ckl_dilate.hpp): the planes, counts and pairs are those of the dilated labels, and the label stage reads the
+// gained pixels' labels beside the tables.  A stream in which nothing is gained goes on as a recompress.
+struct DilateSpec { int connectivity; };
+struct MorphSpec { const ErodeSpec* erode = nullptr; const DilateSpec* dilate = nullptr; };
+void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, uint8_t** out, uint64_t* out_len, const MorphSpec& morph = MorphSpec()) {
+	const ErodeSpec* erode = morph.erode;
+	const DilateSpec* dilate = morph.dilate;
 	if (erode && erode->connectivity != 6 && erode->connectivity != 18 && erode->connectivity != 26)
 		throw Error(CKL_ERR_ARG, "crackle_amd: erode: connectivity must be 6, 18 or 26. Got: " + std::to_string(erode->connectivity));
+	if (dilate && dilate->connectivity != 6 && dilate->connectivity != 18 && dilate->connectivity != 26)
+		throw Error(CKL_ERR_ARG, "crackle_amd: dilate: connectivity must be 6, 18 or 26. Got: " + std::to_string(dilate->connectivity));
 	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
 	const Header head = Header::parse(buf, n);
 	if (head.is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
@@ -2393,9 +2402,10 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, ui
 	e.d_count_vh.ensure(4 * static_cast<size_t>(ns));
 	e.d_stats.ensure(2);
 	CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, 3 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
-	CKL_HIP(hipMemsetAsync(e.d_stats.p, 0, sizeof(unsigned long long), s));
+	CKL_HIP(hipMemsetAsync(e.d_stats.p, 0, 2 * sizeof(unsigned long long), s));      // [0]: the largest label, [1]: ckl_dilate's cursor
 	CKL_HIP(hipEventRecord(e.evd0, s));
 	const dim3 word_grid(static_cast<uint32_t>((e.plane_words + kBlock - 1) / kBlock), ns);
+	unsigned long long gained = 0;
 	if (erode) {
 		const size_t pw = e.plane_words * ns;
 		e.d_erode_bits.ensure(4 * pw);      // P | C | D | K
@@ -2408,6 +2418,29 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, ui
 		hipLaunchKernelGGL(k_erode_planes, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, keep, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
 		CKL_HIP(hipEventRecord(e.evd1, s));
 		src.keep = keep;
+	}
+	else if (dilate) {
+		const size_t pw = e.plane_words * ns;
+		e.d_erode_bits.ensure(2 * pw);      // N | gain
+		e.d_dilate_off.ensure(pw);
+		d.d_run_label.ensure(d.rtot);
+		uint32_t *plane_n = e.d_erode_bits.p, *gain = plane_n + pw;
+		const DilateArgs da = { static_cast<uint32_t>(dilate->connectivity), ns };
+		hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((d.max_rcap + kBlock - 1) / kBlock + 1, 256), ns), dim3(kBlock), 0, s, src, d.d_run_label.p);
+		hipLaunchKernelGGL(k_dilate_nonzero, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, plane_n);
+		hipLaunchKernelGGL(k_dilate_gain, word_grid, dim3(kBlock), 0, s, src.g, da, plane_n, gain, e.d_dilate_off.p, e.d_stats.p + 1);
+		gained = download(e.d_stats.p + 1, 1, s)[0];      // the host sizes the gained pixels' labels
+		if (gained) {
+			e.d_dilate_labels.ensure(gained);
+			hipLaunchKernelGGL(k_dilate_mode, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, da, plane_n, gain, e.d_dilate_off.p, e.d_dilate_labels.p);
+			src.gain = gain; src.gain_off = e.d_dilate_off.p; src.gain_label = e.d_dilate_labels.p;
+			hipLaunchKernelGGL(k_dilate_planes, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
+		}
+		else hipLaunchKernelGGL(k_label_planes_from_runs, word_grid, dim3(kBlock), 0, s, src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
+		CKL_HIP(hipEventRecord(e.evd1, s));
+		// (dilation leaves the largest label what it was)
+		hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, s,
+			d.d_label_map.p, d.total_comp, e.d_stats.p);
 	}
 	else {
 		hipLaunchKernelGGL(k_label_planes_from_runs, word_grid, dim3(kBlock), 0, s, src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
@@ -2448,7 +2481,9 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, ui
 			else if (name == "assembly" || name == "codes_d2h") assembly += m.second;
 			else labels += m.second;      // f:*, flat, l:*, label_table, labels_d2h: the label side, on the host under the crack trail
 		}
-		if (erode) fprintf(stderr, "[ckl erode host ms] tables=%.2f keep_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_erode_device=%.3f\n",
+		if (dilate) fprintf(stderr, "[ckl dilate host ms] tables=%.2f gain_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_dilate_device=%.3f gained=%llu\n",
+			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel, gained);
+		else if (erode) fprintf(stderr, "[ckl erode host ms] tables=%.2f keep_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_erode_device=%.3f\n",
 			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
 		else fprintf(stderr, "[ckl recompress host ms] tables=%.2f label_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_label_planes_from_runs_device=%.3f\n",
 			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
@@ -2639,7 +2674,20 @@ int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int m
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (flags & ~CKL_ERODE_KEEP_BORDER) throw Error(CKL_ERR_ARG, "crackle_amd: erode: unknown flags");
 		const ErodeSpec spec = { connectivity, (flags & CKL_ERODE_KEEP_BORDER) != 0 };
-		recompress(buf, n, markov_model_order, device, out, out_len, &spec);
+		MorphSpec morph;
+		morph.erode = &spec;
+		recompress(buf, n, markov_model_order, device, out, out_len, morph);
+	});
+}
+
+int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: dilate: flags must be 0");
+		const DilateSpec spec = { connectivity };
+		MorphSpec morph;
+		morph.dilate = &spec;
+		recompress(buf, n, markov_model_order, device, out, out_len, morph);
 	});
 }
 

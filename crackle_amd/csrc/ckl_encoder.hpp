@@ -79,6 +79,7 @@ struct ckl_encoder {
 	// planes) and the label stage takes every component's label from these run tables of a decode session (ckl_recompress.hpp)
 	const ckl::dev::RunLabels* label_src = nullptr;
 	DevBuf<uint32_t> d_erode_bits;     // ckl_erode: the planes P | C | D | K of ckl_erode.hpp, [nslices][plane_words] each; K lives through the label stage
+	DevBuf<uint64_t> d_dilate_off, d_dilate_labels;      // ckl_dilate (which keeps its planes N | gain in d_erode_bits): gain_off [nslices][plane_words], gain_label [gained]; they live through the label stage
 	std::vector<std::pair<const char*, double>> host_marks;      // ... and the host timer's marks of that run, for recompress' own line
 	VolumeStats planes_stats;          // max / pairs of the volume the cached planes were built from
 	int64_t planes_dims[3] = { 0, 0, 0 };

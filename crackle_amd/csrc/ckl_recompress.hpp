@@ -25,6 +25,11 @@ struct RunLabels {
 	const uint32_t* ncomp;          // [nslices] components as the label section states them
 	const uint64_t* label_map;      // component -> label
 	const uint32_t* keep = nullptr; // ckl_erode.hpp: [nslices][plane_words], a pixel whose bit is 0 carries label 0 (nullptr: every pixel keeps its label)
+	// ckl_dilate.hpp: a pixel whose bit is set in gain [nslices][plane_words] carries gain_label[gain_off[its word] + the set
+	// bits of the word below it] instead of its run's label (nullptr: no pixel does)
+	const uint32_t* gain = nullptr;
+	const uint64_t* gain_off = nullptr;
+	const uint64_t* gain_label = nullptr;
 
 	// label of run `run` of slice zi; everything read from the tables is clamped as k_paint_window clamps it
 	__device__ __forceinline__ uint64_t label_of(uint32_t zi, uint32_t run) const {
@@ -32,6 +37,15 @@ struct RunLabels {
 		if (!n) return 0ull;
 		const uint32_t cc = run_cc[rbase[zi] + (run < n ? run : n - 1u)];
 		return cc < ncomp[zi] ? label_map[comp_off[zi] + cc] : 0ull;
+	}
+	// true, and the label in l: pixel (x, y) of slice zi is a gained one
+	__device__ __forceinline__ bool gained(uint32_t zi, uint32_t x, uint32_t y, uint64_t& l) const {
+		if (!gain) return false;
+		const uint64_t at = zi * g.plane_words + static_cast<uint64_t>(y) * g.row_words + (x >> 5);
+		const uint32_t gw = gain[at], bit = 1u << (x & 31u);
+		if (!(gw & bit)) return false;
+		l = gain_label[gain_off[at] + __popc(gw & (bit - 1u))];
+		return true;
 	}
 	// the run of pixel (x, y) of slice zi
 	__device__ __forceinline__ uint32_t run_at(uint32_t zi, uint32_t x, uint32_t y) const {
@@ -151,7 +165,9 @@ __global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
 	const uint32_t y = pix / t.g.sx;
 	const uint32_t x = pix - y * t.g.sx;
 	const bool kept = !t.keep || ((t.keep[zi * t.g.plane_words + static_cast<uint64_t>(y) * t.g.row_words + (x >> 5)] >> (x & 31u)) & 1u);
-	mapping[comp_off[zi] + c] = kept ? t.label_of(zi, t.run_at(zi, x, y)) : 0ull;
+	uint64_t l;
+	if (!t.gained(zi, x, y, l)) l = kept ? t.label_of(zi, t.run_at(zi, x, y)) : 0ull;
+	mapping[comp_off[zi] + c] = l;
 }
 
 }  // namespace dev

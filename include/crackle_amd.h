@@ -519,6 +519,26 @@ int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int d
 int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device,
               uint8_t** out, uint64_t* out_len);
 
+/* Morphological dilation of a stream's labels by one voxel (meant as fastmorph's multilabel dilate with
+ * background_only; the reference has no such function): the stream that ckl_compress gives for the dilated
+ * volume, written as ckl_erode writes its own (FLAT labels, format version 1, markov_model_order < 0: keep the
+ * input's, the input's data width and fortran_order flag).  This project's definition, one iteration per call: a
+ * voxel whose label is not 0 keeps it.  For a voxel with label 0 the counted neighbours are the 6, 18 or 26
+ * (`connectivity`) offsets of ckl_erode's structuring element that lie inside the volume and carry a label other
+ * than 0; without any the voxel stays 0, otherwise it takes the label that occurs most often among them, and among
+ * labels tied for most often the smallest, compared as unsigned 64-bit values (the tie rule is this project's and
+ * was not checked against fastmorph).  Neighbours outside the volume do not exist, so there is no border flag:
+ * `flags` must be 0.  Labels are compared, not runs or components.  No voxel is decoded: the decoder runs up to its
+ * run tables, the gained pixels are found from "label != 0" bit planes (k_dilate_nonzero, k_dilate_gain), every
+ * gained pixel's label is the mode of its neighbours' labels read through the runs (k_dilate_mode), the encoder's
+ * planes are written from both (k_dilate_planes), and the encoder's crack and label stages follow, the label stage
+ * reading the gained labels beside the tables.  A stream in which nothing is gained comes back as ckl_recompress
+ * returns it.  FLAT, pin and version 0 streams; signed streams, another connectivity and flags other than 0 are
+ * CKL_ERR_ARG; the stream of an empty volume comes back as ckl_recompress returns it, without a device.  A damaged
+ * slice fails as in ckl_decompress.  *out is released with ckl_free. */
+int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device,
+               uint8_t** out, uint64_t* out_len);
+
 /* Native form of crackle.operations.zsplit's range helper (crackle/operations.py:550-623):
  * the stream of slices [z_start, z_end) of a FLAT stream, without decoding (host only).
  * *out is released with ckl_free. */

@@ -171,6 +171,16 @@ __device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t* lds) {
 	__syncthreads();
 	return tot;
 }
+// the workgroup's largest v (not 0) into *out by one atomicMax; *out zeroed by the host
+__device__ __forceinline__ void block_max_into(unsigned long long mx, unsigned long long* lds, unsigned long long* out) {
+	for (int d = kWave / 2; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(mx, d, kWave); mx = o > mx ? o : mx; }
+	if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mx;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (int w = 1; w < kWaves; w++) mx = lds[w] > mx ? lds[w] : mx;
+		if (mx) atomicMax(out, mx);
+	}
+}
 
 // ---- CRC-32C in GF(2)[x]/P, reflected (bit 31 <-> x^0) -------------------------
 constexpr uint32_t kCrcPoly = 0x82F63B78u;

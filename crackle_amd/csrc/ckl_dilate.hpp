@@ -42,25 +42,11 @@ struct DilateArgs {
 __global__ void __launch_bounds__(kBlock) k_dilate_nonzero(RunLabels t, const uint64_t* __restrict__ run_label, uint32_t* __restrict__ planeN) {
 	const RunGeom& g = t.g;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	if (i >= g.plane_words) return;
-	const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-	const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
-	const uint64_t at = zi * g.plane_words + i;
-	const uint32_t valid = g.valid_mask(w);
-	const uint32_t b = g.breaks(zi, y, w);
-	const SliceRunLabels lab(t, run_label, zi);
-	uint32_t rc = t.word_base[at] - 1u;      // the run that reaches into the word from the left
-	uint64_t lc = w ? lab(rc) : 0ull;
-	uint32_t nz = 0;
-	uint32_t rest = (b | 1u) & valid;
-	while (rest) {
-		const uint32_t x = __builtin_ctz(rest);
-		rest &= rest - 1u;
-		if ((b >> x) & 1u) lc = lab(++rc);
-		if (lc) nz |= bits_from_to(x, rest ? __builtin_ctz(rest) : 32u);
-	}
-	planeN[at] = nz & valid;
+	const PlaneWord pw(g, zi, i);
+	uint32_t same_as_before;      // (unused)
+	planeN[pw.at] = nonzero_bits(t, run_label, zi, pw, g.breaks(zi, pw.y, pw.w), same_as_before);
 }
 
 // One thread per word: gain and gain_off (header comment).  *cursor zeroed by the host; afterwards it holds the number of
@@ -71,13 +57,13 @@ __global__ void __launch_bounds__(kBlock) k_dilate_gain(
 	__shared__ uint32_t s_scan[kWaves];
 	__shared__ unsigned long long s_base;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	const bool live = i < g.plane_words;
 	const uint64_t at = zi * g.plane_words + i;
 	uint32_t gw = 0;
 	if (live) {
-		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
+		const PlaneWord pw(g, zi, i);
+		const uint32_t y = pw.y, w = pw.w;
 		const bool first = w == 0u, last = w + 1u == g.row_words;
 		// the word of row (y + dy, zi + dz), the last bit of the word before it and the first bit of the word after it
 		auto row = [&](int dy, int dz, uint32_t& c, uint32_t& l, uint32_t& r) {
@@ -97,7 +83,7 @@ __global__ void __launch_bounds__(kBlock) k_dilate_gain(
 		if (a.connectivity == 6u) near |= fc;
 		else if (a.connectivity == 18u) near |= fc | side(fc, fl, fr) | dc;
 		else near |= fc | dc | side(fc | dc, fl | dl, fr | dr);
-		gw = near & ~nc & g.valid_mask(w);
+		gw = near & ~nc & pw.valid;
 		gain[at] = gw;
 	}
 	uint32_t v[1] = { static_cast<uint32_t>(__popc(gw)) }, total[1];
@@ -155,9 +141,8 @@ __global__ void __launch_bounds__(kBlock) k_dilate_mode(
 		uint32_t bits = gw;
 		for (uint32_t j = item - s_start[tw]; j; j--) bits &= bits - 1u;
 		const uint32_t xb = __builtin_ctz(bits);      // (bits != 0: the word has more than item - start gained pixels)
-		const uint64_t i = i0 + tw;
-		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
+		const PlaneWord pw(g, zi, i0 + tw);
+		const uint32_t y = pw.y, w = pw.w;
 		const bool first = w == 0u, last = w + 1u == g.row_words;
 		// the labels, row r = 3 * (dz + 1) + (dy + 1): 0 where there is nothing to count
 		uint64_t ll[kDilateRows], lc[kDilateRows], lr[kDilateRows];
@@ -216,7 +201,7 @@ __global__ void __launch_bounds__(kBlock) k_dilate_mode(
 			const uint32_t n = my_count[k * kBlock];
 			if (n > best_n || (n == best_n && l < best)) { best = l; best_n = n; }
 		}
-		gain_label[gain_off[zi * g.plane_words + i] + __popc(gw & ((1u << xb) - 1u))] = best;
+		gain_label[gain_off[pw.at] + __popc(gw & ((1u << xb) - 1u))] = best;
 	}
 }
 
@@ -238,14 +223,11 @@ __global__ void __launch_bounds__(kBlock) k_dilate_planes(
 	__shared__ uint32_t s_red[kWaves];
 	const RunGeom& g = t.g;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	uint32_t nv = 0, nh = 0, nw = 0;
 	if (i < g.plane_words) {
-		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
-		const uint64_t at = zi * g.plane_words + i;
+		const auto [y, w, valid, at] = PlaneWord(g, zi, i);
 		const uint64_t up = at - g.row_words;      // (used with y >= 1 only)
-		const uint32_t valid = g.valid_mask(w);
 		const SliceRunLabels lab(t, run_label, zi);
 		const uint32_t b = g.breaks(zi, y, w), bu = y ? g.breaks(zi, y - 1u, w) : 0u;
 		const uint32_t gw = t.gain[at], gu = y ? t.gain[up] : 0u;
@@ -280,12 +262,7 @@ __global__ void __launch_bounds__(kBlock) k_dilate_planes(
 		planeV[at] = v; planeH[at] = h;
 		nv = __popc(v); nh = __popc(h);
 	}
-	nv = block_sum(nv, s_red); nh = block_sum(nh, s_red); nw = block_sum(nw, s_red);
-	if (threadIdx.x == 0) {
-		if (nv) atomicAdd(counts + zi, nv);
-		if (nh) atomicAdd(counts + nslices + zi, nh);
-		if (nw) atomicAdd(counts + 2u * nslices + zi, nw);
-	}
+	add_plane_counts(nv, nh, nw, s_red, counts, nslices, zi);
 }
 
 }  // namespace dev

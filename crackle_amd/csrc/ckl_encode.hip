@@ -10,15 +10,14 @@
 //   cc3d::connected_components2d_4 + relabel        src/cc3d.hpp:114-144, 257-369        ckl_runs.hpp (runs of the label planes)
 //   labels::encode_flat                             src/labels.hpp:30-155      k_run_resolve (crc), k_mapping_comps + sort/unique
 //   stream assembly                                 src/crackle.hpp:171-216    host
-// and crackle.operations.recompress (crackle/operations.py:664-857) without the voxels: ckl_recompress.hpp + recompress()
+// crackle.operations.recompress without the voxels (ckl_recompress.hip) comes in through encode_from_planes; of its
+// kernels the label stage here launches k_component_labels_from_runs (ckl_recompress.hpp).
 #include "ckl_encoder.hpp"
 #include "ckl_decoder.hpp"
 #include "ckl_runs.hpp"
 #include "ckl_strips.hpp"
 #include "ckl_trail.hpp"
 #include "ckl_recompress.hpp"
-#include "ckl_erode.hpp"
-#include "ckl_dilate.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1256,10 +1255,6 @@ VolumeStats volume_stats(ckl_encoder& e, const LABEL* labels, uint64_t voxels) {
 	return st;
 }
 
-// the label planes of the session, V then H, as the kernels take them
-inline uint32_t* plane_v(const ckl_encoder& e) { return e.d_planes.p; }
-inline uint32_t* plane_h(const ckl_encoder& e, uint32_t ns) { return e.d_planes.p + e.plane_words * ns; }
-
 // ckl_encoder_stats left the planes of exactly this volume behind (single use: the callers clear planes_for)
 inline bool planes_cached(const ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, int64_t sz) {
 	return e.planes_for == labels && e.planes_dims[0] == sx && e.planes_dims[1] == sy && e.planes_dims[2] == sz;
@@ -2047,9 +2042,11 @@ uint64_t flat_section(ckl_encoder& e, uint64_t N, int stored_width, int componen
 	return 8 + static_cast<uint64_t>(nu) * stored_width + static_cast<uint64_t>(ns) * component_width + N * static_cast<uint64_t>(byte_width(nu));
 }
 
+}  // namespace
+
 // The stream's header as the volume's statistics decide it (crackle.hpp:50-64, 233-235) unless the overrides do;
 // of an empty volume (all statistics 0) it is the whole stream (crackle.hpp:96-98).  num_label_bytes comes later.
-Header stream_header(int data_width, int64_t sx, int64_t sy, int64_t sz, const VolumeStats& st, bool allow_pins, bool fortran_order, uint64_t markov_model_order, const ckl_encode_overrides* ov) {
+Header ckl::stream_header(int data_width, int64_t sx, int64_t sy, int64_t sz, const VolumeStats& st, bool allow_pins, bool fortran_order, uint64_t markov_model_order, const ckl_encode_overrides* ov) {
 	Header head;
 	head.crack_format = IMPERMISSIBLE;
 	head.label_format = PINS_VARIABLE_WIDTH;
@@ -2073,19 +2070,44 @@ Header stream_header(int data_width, int64_t sx, int64_t sy, int64_t sz, const V
 	head.is_sorted = true;
 	return head;
 }
-inline std::vector<uint8_t> header_bytes(const Header& head) {
-	std::vector<uint8_t> hb;
-	head.write(hb);
-	return hb;
+
+void ckl::check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_signed) {
+	if (is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
+	if (dtype_bytes != 1 && dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8) throw Error(CKL_ERR_ARG, "crackle_amd: dtype width must be 1, 2, 4 or 8 bytes");
+	if (sx < 0 || sy < 0 || sz < 0) throw Error(CKL_ERR_ARG, "crackle_amd: negative dimension");
+	if (sx > 0x7FFFFFF0ll || sy > 0x7FFFFFF0ll || sz > 0x7FFFFFF0ll) throw Error(CKL_ERR_ARG, "crackle_amd: dimension too large");
+	// (slices of 2^30 or more pixels encode into streams this decoder refuses, and one such encode faulted on the
+	// device: until the 32-bit arithmetic behind that is found, the limit is 2^30 crack vertices)
+	if (static_cast<uint64_t>(sx + 1) * static_cast<uint64_t>(sy + 1) >= (1ull << 30)) throw Error(CKL_ERR_ARG, "crackle_amd: slices of 2^30 or more crack vertices are not supported");
 }
 
+void ckl::planes_adopt(ckl_encoder& e, uint32_t row_words, uint64_t plane_words, uint32_t ns, uint32_t count_rows) {
+	e.row_words = row_words;
+	e.plane_words = plane_words;
+	e.d_planes.ensure(2 * plane_words * ns);
+	e.d_count_vh.ensure(4 * static_cast<size_t>(ns));
+	CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, count_rows * static_cast<size_t>(ns) * sizeof(uint32_t), e.stream));
+}
+
+void ckl::planes_adopt_counts(ckl_encoder& e, const std::vector<uint32_t>& counts, uint32_t ns) {
+	e.count_v.assign(counts.begin(), counts.begin() + ns);
+	e.count_h.assign(counts.begin() + ns, counts.begin() + 2 * static_cast<size_t>(ns));
+}
+
+namespace {
+
+// what a run makes of its volume: ckl_encoder_run's arguments (include/crackle_amd.h)
+struct EncodeRequest {
+	bool allow_pins = false, fortran_order = false;
+	uint64_t markov_model_order = 0;
+	bool optimize_pins = false, auto_bgcolor = true;
+	int64_t manual_bgcolor = 0;
+	const ckl_encode_overrides* overrides = nullptr;
+};
+
 template <typename LABEL>
-void encode_typed(
-	ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz,
-	bool allow_pins, bool fortran_order, uint64_t markov_model_order,
-	bool optimize_pins, bool auto_bgcolor, int64_t manual_bgcolor,
-	const ckl_encode_overrides* ov, uint8_t** out, uint64_t* out_len
-) {
+void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz, const EncodeRequest& req, uint8_t** out, uint64_t* out_len) {
+	const ckl_encode_overrides* const ov = req.overrides;
 	const uint64_t voxels = static_cast<uint64_t>(sx) * sy * sz;
 	hipStream_t s = e.stream;
 	CKL_HIP(hipEventRecord(e.ev0, s));
@@ -2113,11 +2135,11 @@ void encode_typed(
 		graph_done = true;
 		ht.mark("graph");
 	}
-	Header head = stream_header(static_cast<int>(sizeof(LABEL)), sx, sy, sz, st, allow_pins, fortran_order, markov_model_order, ov);
+	Header head = stream_header(static_cast<int>(sizeof(LABEL)), sx, sy, sz, st, req.allow_pins, req.fortran_order, req.markov_model_order, ov);
 	const int stored_width = head.stored_data_width;
 	e.uploads_by_kernel = head.label_format == FLAT;
 	if (voxels == 0) { hand_out(header_bytes(head), OutAlloc::MALLOC, out, out_len); return; }
-	if (optimize_pins) throw Error(CKL_ERR_ARG, "crackle_amd: allow_pins=2 (find_optimal_pins) is out of scope");
+	if (req.optimize_pins) throw Error(CKL_ERR_ARG, "crackle_amd: allow_pins=2 (find_optimal_pins) is out of scope");
 	if (head.label_format != FLAT && head.label_format != PINS_VARIABLE_WIDTH) throw Error(CKL_ERR_ARG, "crackle_amd: unsupported label format");
 	if (head.markov_model_order > 13) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order > 13 is not supported on device");
 
@@ -2204,7 +2226,7 @@ void encode_typed(
 			if (N > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
 			e.d_cc_volume.ensure(voxels);
 			launch_paint_components(s2, plane_v(e), e.row_words, e.plane_words, sx, sy, sz, e.d_word_base.p, e.d_rbase.p, e.d_run_cc.p, e.d_comp_off.p, 0u, e.d_cc_volume.p);
-			pins_binary = pins_section_plain<LABEL>(e, labels, e.d_cc_volume.p, e.d_mapping.p, sx, sy, sz, N, fr.ncomp, head.pin_index_width(), stored_width, auto_bgcolor, manual_bgcolor);
+			pins_binary = pins_section_plain<LABEL>(e, labels, e.d_cc_volume.p, e.d_mapping.p, sx, sy, sz, N, fr.ncomp, head.pin_index_width(), stored_width, req.auto_bgcolor, req.manual_bgcolor);
 			label_bytes = pins_binary.size();
 		}
 		else {
@@ -2329,166 +2351,34 @@ void encode_typed(
 		host_out_free(o);
 		throw;
 	}
-	if (e.label_src) e.host_marks = ht.marks;      // recompress folds them into its own line
+	if (e.label_src) e.host_marks = ht.marks;      // recompress (ckl_recompress.hip) folds them into its own line
 	*out = o;
 	*out_len = total;
 }
 
-// crackle.operations.recompress (crackle/operations.py:664-857 decodes slabs to voxels and compresses them again).
-// Here no voxel exists anywhere: a TABLES run of the decoder leaves the runs of every slice and the label of every
-// component, k_label_planes_from_runs (ckl_recompress.hpp) writes the encoder's planes and the volume's statistics
-// from them, and encode_typed goes on as it does from cached planes, with the label stage reading the same tables.
-// The bytes are those of compress(decompress(stream), markov_model_order): the planes, max label and pixel pairs are
-// functions of the labels alone, and everything behind them is the encoder's own.
-void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_signed);
-// erode (ckl_erode: the same road with another volume at its end): the planes, counts, pairs and maximum are those of the
-// eroded labels (ckl_erode.hpp) and the label stage reads the keep plane beside the tables; nullptr: recompress
-struct ErodeSpec { int connectivity; bool keep_border; };
-// dilate (ckl_dilate.hpp): the planes, counts and pairs are those of the dilated labels, and the label stage reads the
-// gained pixels' labels beside the tables.  A stream in which nothing is gained goes on as a recompress.
-struct DilateSpec { int connectivity; };
-struct MorphSpec { const ErodeSpec* erode = nullptr; const DilateSpec* dilate = nullptr; };
-void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, uint8_t** out, uint64_t* out_len, const MorphSpec& morph = MorphSpec()) {
-	const ErodeSpec* erode = morph.erode;
-	const DilateSpec* dilate = morph.dilate;
-	if (erode && erode->connectivity != 6 && erode->connectivity != 18 && erode->connectivity != 26)
-		throw Error(CKL_ERR_ARG, "crackle_amd: erode: connectivity must be 6, 18 or 26. Got: " + std::to_string(erode->connectivity));
-	if (dilate && dilate->connectivity != 6 && dilate->connectivity != 18 && dilate->connectivity != 26)
-		throw Error(CKL_ERR_ARG, "crackle_amd: dilate: connectivity must be 6, 18 or 26. Got: " + std::to_string(dilate->connectivity));
-	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
-	const Header head = Header::parse(buf, n);
-	if (head.is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
-	const uint64_t order = markov_order < 0 ? static_cast<uint64_t>(head.markov_model_order) : static_cast<uint64_t>(markov_order);
-	if (order > 15) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [0, 15]");
-	const int64_t sx = head.sx, sy = head.sy, sz = head.sz;
-	check_dims(sx, sy, sz, head.data_width, 0);
-	if (head.voxels() == 0) {
-		hand_out(header_bytes(stream_header(head.data_width, sx, sy, sz, VolumeStats(), false, head.fortran_order, order, nullptr)), OutAlloc::MALLOC, out, out_len);
-		return;
-	}
-	select_device(device);      // (what came before needs none: refusals and streams without voxels are the host's)
-	const bool prof = getenv("CKL_PROFILE") != nullptr;
-	auto t_prev = std::chrono::steady_clock::now();
-	auto lap = [&]() {
-		const auto now = std::chrono::steady_clock::now();
-		const double ms = std::chrono::duration<double, std::milli>(now - t_prev).count();
-		t_prev = now;
-		return ms;
-	};
-	DecoderPtr dec;
-	const int rc = open_decoder(buf, n, 0, -1, device, dec);
-	if (rc != CKL_OK) throw Error(rc, ckl_last_error());
-	ckl_decoder& d = *dec;
-	enter(&d);
-	decoder_run(d, { Goal::TABLES });      // a damaged slice raises here, as for a decode
-	CKL_HIP(hipStreamSynchronize(d.stream));
-	const double ms_tables = lap();
+}  // namespace
 
-	ckl_encoder* raw = nullptr;
-	if (ckl_encoder_create(sx, sy, sz, head.data_width, device, &raw) != CKL_OK) throw Error(CKL_ERR_RUNTIME, ckl_last_error());
-	const EncoderPtr enc(raw);
-	ckl_encoder& e = *enc;
-	enter(&e);
-	hipStream_t s = e.stream;
-	const uint32_t ns = d.nslices;
-	const RunArrays ra = run_arrays(d);
-	RunLabels src;
-	src.g = run_geom(d);
-	src.word_base = ra.word_base; src.rbase = ra.rbase; src.run_cc = ra.run_cc; src.nruns = ra.nruns;
-	src.comp_off = d.d_comp_off.p; src.ncomp = d.d_ncomp_expect.p; src.label_map = d.d_label_map.p;
-	e.row_words = d.row_words;
-	e.plane_words = d.plane_words;
-	e.d_planes.ensure(2 * e.plane_words * ns);
-	e.d_count_vh.ensure(4 * static_cast<size_t>(ns));
-	e.d_stats.ensure(2);
-	CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, 3 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
-	CKL_HIP(hipMemsetAsync(e.d_stats.p, 0, 2 * sizeof(unsigned long long), s));      // [0]: the largest label, [1]: ckl_dilate's cursor
-	CKL_HIP(hipEventRecord(e.evd0, s));
-	const dim3 word_grid(static_cast<uint32_t>((e.plane_words + kBlock - 1) / kBlock), ns);
-	unsigned long long gained = 0;
-	if (erode) {
-		const size_t pw = e.plane_words * ns;
-		e.d_erode_bits.ensure(4 * pw);      // P | C | D | K
-		d.d_run_label.ensure(d.rtot);       // (PAINT's scratch of the decode session: one label per run, at the runs' own bases)
-		uint32_t *plane_p = e.d_erode_bits.p, *plane_c = plane_p + pw, *plane_d = plane_c + pw, *keep = plane_d + pw;
-		const ErodeArgs ea = { static_cast<uint32_t>(erode->connectivity), erode->keep_border ? 1u : 0u, ns };
-		hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((d.max_rcap + kBlock - 1) / kBlock + 1, 256), ns), dim3(kBlock), 0, s, src, d.d_run_label.p);
-		hipLaunchKernelGGL(k_erode_terms, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, ea, plane_p, plane_c, plane_d);
-		hipLaunchKernelGGL(k_erode_keep, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, ea, plane_p, plane_c, plane_d, keep, e.d_stats.p);
-		hipLaunchKernelGGL(k_erode_planes, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, keep, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
-		CKL_HIP(hipEventRecord(e.evd1, s));
-		src.keep = keep;
-	}
-	else if (dilate) {
-		const size_t pw = e.plane_words * ns;
-		e.d_erode_bits.ensure(2 * pw);      // N | gain
-		e.d_dilate_off.ensure(pw);
-		d.d_run_label.ensure(d.rtot);
-		uint32_t *plane_n = e.d_erode_bits.p, *gain = plane_n + pw;
-		const DilateArgs da = { static_cast<uint32_t>(dilate->connectivity), ns };
-		hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((d.max_rcap + kBlock - 1) / kBlock + 1, 256), ns), dim3(kBlock), 0, s, src, d.d_run_label.p);
-		hipLaunchKernelGGL(k_dilate_nonzero, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, plane_n);
-		hipLaunchKernelGGL(k_dilate_gain, word_grid, dim3(kBlock), 0, s, src.g, da, plane_n, gain, e.d_dilate_off.p, e.d_stats.p + 1);
-		gained = download(e.d_stats.p + 1, 1, s)[0];      // the host sizes the gained pixels' labels
-		if (gained) {
-			e.d_dilate_labels.ensure(gained);
-			hipLaunchKernelGGL(k_dilate_mode, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, da, plane_n, gain, e.d_dilate_off.p, e.d_dilate_labels.p);
-			src.gain = gain; src.gain_off = e.d_dilate_off.p; src.gain_label = e.d_dilate_labels.p;
-			hipLaunchKernelGGL(k_dilate_planes, word_grid, dim3(kBlock), 0, s, src, d.d_run_label.p, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
-		}
-		else hipLaunchKernelGGL(k_label_planes_from_runs, word_grid, dim3(kBlock), 0, s, src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
-		CKL_HIP(hipEventRecord(e.evd1, s));
-		// (dilation leaves the largest label what it was)
-		hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, s,
-			d.d_label_map.p, d.total_comp, e.d_stats.p);
-	}
-	else {
-		hipLaunchKernelGGL(k_label_planes_from_runs, word_grid, dim3(kBlock), 0, s, src, plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
-		CKL_HIP(hipEventRecord(e.evd1, s));
-		hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, s,
-			d.d_label_map.p, d.total_comp, e.d_stats.p);
-	}
-	const std::vector<uint32_t> c = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), s);
-	const std::vector<unsigned long long> mx = download(e.d_stats.p, 1, s);
-	float ms_kernel = 0.f;
-	CKL_HIP(hipEventElapsedTime(&ms_kernel, e.evd0, e.evd1));
-	e.count_v.assign(c.begin(), c.begin() + ns);
-	e.count_h.assign(c.begin() + ns, c.begin() + 2 * static_cast<size_t>(ns));
-	// lib::pixel_pairs (lib.hpp:249-256): equal neighbours in x-fastest order — inside the rows every pair that V does not
-	// mark, and the wrap-arounds the kernel counted
-	VolumeStats st;
-	st.max_label = mx[0];
-	for (uint32_t zi = 0; zi < ns; zi++) st.pairs += static_cast<uint64_t>(sx - 1) * sy - e.count_v[zi] + c[2 * static_cast<size_t>(ns) + zi];
+// (declared in ckl_encoder.hpp) encode_typed goes on as it does from cached planes, with the label stage reading
+// `labels`: the planes, max label and pixel pairs are functions of the labels alone, and everything behind them is the
+// encoder's own, so the bytes are those of compress() of the volume the tables describe.
+void ckl::encode_from_planes(
+	ckl_encoder& e, const RunLabels& labels, int64_t sx, int64_t sy, int64_t sz, int data_width, bool fortran_order,
+	uint64_t markov_model_order, const VolumeStats& st, const std::vector<uint32_t>& counts, uint8_t** out, uint64_t* out_len
+) {
+	planes_adopt_counts(e, counts, static_cast<uint32_t>(sz));
 	e.planes_stats = st;
 	e.planes_deferred = false;
-	e.label_src = &src;
-	e.planes_for = &src;
 	e.planes_dims[0] = sx; e.planes_dims[1] = sy; e.planes_dims[2] = sz;
-	const double ms_planes = lap();
-	try {
-		with_label_type(head.data_width, [&](auto t) {
-			encode_typed<typename decltype(t)::type>(e, nullptr, sx, sy, sz, false, head.fortran_order, order, false, true, 0, nullptr, out, out_len);
-		});
-	}
-	catch (...) { e.label_src = nullptr; throw; }
-	e.label_src = nullptr;
-	if (prof) {
-		double graph = 0, cracks = 0, labels = 0, assembly = 0;
-		for (const auto& m : e.host_marks) {
-			const std::string name = m.first;
-			if (name == "planes" || name == "graph") graph += m.second;
-			else if (name == "cracks") cracks += m.second;
-			else if (name == "assembly" || name == "codes_d2h") assembly += m.second;
-			else labels += m.second;      // f:*, flat, l:*, label_table, labels_d2h: the label side, on the host under the crack trail
-		}
-		if (dilate) fprintf(stderr, "[ckl dilate host ms] tables=%.2f gain_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_dilate_device=%.3f gained=%llu\n",
-			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel, gained);
-		else if (erode) fprintf(stderr, "[ckl erode host ms] tables=%.2f keep_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_erode_device=%.3f\n",
-			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
-		else fprintf(stderr, "[ckl recompress host ms] tables=%.2f label_planes=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f k_label_planes_from_runs_device=%.3f\n",
-			ms_tables, ms_planes, graph, cracks, labels, assembly, ms_kernel);
-	}
+	struct Source {
+		ckl_encoder& e;
+		Source(ckl_encoder& enc, const RunLabels* l) : e(enc) { e.label_src = l; e.planes_for = l; }
+		~Source() { e.label_src = nullptr; e.planes_for = nullptr; }
+	} source(e, &labels);
+	const EncodeRequest req = { false, fortran_order, markov_model_order };      // (the rest: no pins, the background colour chosen, no overrides)
+	with_label_type(data_width, [&](auto t) { encode_typed<typename decltype(t)::type>(e, nullptr, sx, sy, sz, req, out, out_len); });
 }
+
+namespace {
 
 // reencode_with_markov_order (src/crackle.hpp:858-984).  The reference takes every slice's
 // code apart into symbols and packs them again; here the decoder rasterises the codes into the
@@ -2543,17 +2433,11 @@ void reencode_markov(const uint8_t* buf, uint64_t n, int markov_order, int devic
 		hipStream_t s = e.stream;
 		const uint32_t ns = head.sz;
 		const bool permissible = head.crack_format == PERMISSIBLE;
-		e.row_words = row_words;
-		e.plane_words = plane_words;
-		e.d_planes.ensure(2 * plane_words * ns);
-		e.d_count_vh.ensure(4 * static_cast<size_t>(ns));
-		CKL_HIP(hipMemsetAsync(e.d_count_vh.p, 0, 2 * static_cast<size_t>(ns) * sizeof(uint32_t), s));
+		planes_adopt(e, row_words, plane_words, ns, 2);
 		hipLaunchKernelGGL(k_planes_from_cracks, dim3(static_cast<uint32_t>((plane_words + kBlock - 1) / kBlock), ns), dim3(kBlock), 0, s,
 			cv, ch, head.sx, head.sy, row_words, plane_words, permissible ? 1u : 0u,
 			plane_v(e), plane_h(e, ns), e.d_count_vh.p, ns);
-		std::vector<uint32_t> c = download(e.d_count_vh.p, 2 * static_cast<size_t>(ns), s);
-		e.count_v.assign(c.begin(), c.begin() + ns);
-		e.count_h.assign(c.begin() + ns, c.end());
+		planes_adopt_counts(e, download(e.d_count_vh.p, 2 * static_cast<size_t>(ns), s), ns);
 		lap("planes");
 		graph_pass(e, head.sx, head.sy, head.sz, graph_format(permissible));
 		lap("graph");
@@ -2589,16 +2473,6 @@ void reencode_markov(const uint8_t* buf, uint64_t n, int markov_order, int devic
 	catch (...) { host_out_free(o); throw; }
 	*out = o;
 	*out_len = total;
-}
-
-void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_signed) {
-	if (is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
-	if (dtype_bytes != 1 && dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8) throw Error(CKL_ERR_ARG, "crackle_amd: dtype width must be 1, 2, 4 or 8 bytes");
-	if (sx < 0 || sy < 0 || sz < 0) throw Error(CKL_ERR_ARG, "crackle_amd: negative dimension");
-	if (sx > 0x7FFFFFF0ll || sy > 0x7FFFFFF0ll || sz > 0x7FFFFFF0ll) throw Error(CKL_ERR_ARG, "crackle_amd: dimension too large");
-	// (slices of 2^30 or more pixels encode into streams this decoder refuses, and one such encode faulted on the
-	// device: until the 32-bit arithmetic behind that is found, the limit is 2^30 crack vertices)
-	if (static_cast<uint64_t>(sx + 1) * static_cast<uint64_t>(sy + 1) >= (1ull << 30)) throw Error(CKL_ERR_ARG, "crackle_amd: slices of 2^30 or more crack vertices are not supported");
 }
 
 }  // namespace
@@ -2644,9 +2518,9 @@ int ckl_encoder_run(
 		enter(e);
 		drain_host_copy(*e);      // the previous run's codes are still on their way out of d_codes_out
 		const auto t_run0 = std::chrono::steady_clock::now();
+		const EncodeRequest req = { allow_pins != 0, fortran_order != 0, markov_model_order, optimize_pins != 0, auto_bgcolor != 0, manual_bgcolor, overrides };
 		with_label_type(e->dtype_bytes, [&](auto t) {
-			encode_typed(*e, static_cast<const typename decltype(t)::type*>(labels_device), sx, sy, sz, allow_pins != 0, fortran_order != 0,
-				markov_model_order, optimize_pins != 0, auto_bgcolor != 0, manual_bgcolor, overrides, out, out_len);
+			encode_typed(*e, static_cast<const typename decltype(t)::type*>(labels_device), sx, sy, sz, req, out, out_len);
 		});
 		if (getenv("CKL_PROFILE")) {
 			fprintf(stderr, "[ckl encoder_run ms] encode=%.2f\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_run0).count());
@@ -2659,35 +2533,6 @@ int ckl_reencode_markov(const uint8_t* buf, uint64_t n, int markov_model_order, 
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		select_device(device);
 		reencode_markov(buf, n, markov_model_order, device, out, out_len);
-	});
-}
-
-int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
-	return guard([&] {
-		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		recompress(buf, n, markov_model_order, device, out, out_len);
-	});
-}
-
-int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
-	return guard([&] {
-		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		if (flags & ~CKL_ERODE_KEEP_BORDER) throw Error(CKL_ERR_ARG, "crackle_amd: erode: unknown flags");
-		const ErodeSpec spec = { connectivity, (flags & CKL_ERODE_KEEP_BORDER) != 0 };
-		MorphSpec morph;
-		morph.erode = &spec;
-		recompress(buf, n, markov_model_order, device, out, out_len, morph);
-	});
-}
-
-int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
-	return guard([&] {
-		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
-		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: dilate: flags must be 0");
-		const DilateSpec spec = { connectivity };
-		MorphSpec morph;
-		morph.dilate = &spec;
-		recompress(buf, n, markov_model_order, device, out, out_len, morph);
 	});
 }
 

@@ -1,5 +1,6 @@
-// The encode session (created and run by ckl_encode.hip) and what the pin stage (ckl_encode_pins.hip)
-// needs of it: the session's streams and scratch, the small transfers, the host timer and enter().
+// The encode session (created and run by ckl_encode.hip) and what the pin stage (ckl_encode_pins.hip) and the road
+// from a decode session's tables (ckl_recompress.hip) need of it: the session's streams and scratch, the small
+// transfers, the host timer, enter(), and that road's door (planes_adopt, encode_from_planes).
 #pragma once
 
 #include "ckl_common.hpp"
@@ -75,12 +76,11 @@ struct ckl_encoder {
 	const void* trail_for = nullptr;
 	bool trail_perm = false;
 	int trail_order = 0;
-	// ckl_recompress: there is no volume.  The planes stand in d_planes (planes_stats, count_v / count_h as for cached
-	// planes) and the label stage takes every component's label from these run tables of a decode session (ckl_recompress.hpp)
+	// encode_from_planes (ckl_recompress.hip's road): there is no volume.  The planes stand in d_planes (planes_stats, count_v /
+	// count_h as for cached planes) and the label stage takes every component's label from these run tables of a decode
+	// session (ckl_recompress.hpp).  Set for the length of that call only.
 	const ckl::dev::RunLabels* label_src = nullptr;
-	DevBuf<uint32_t> d_erode_bits;     // ckl_erode: the planes P | C | D | K of ckl_erode.hpp, [nslices][plane_words] each; K lives through the label stage
-	DevBuf<uint64_t> d_dilate_off, d_dilate_labels;      // ckl_dilate (which keeps its planes N | gain in d_erode_bits): gain_off [nslices][plane_words], gain_label [gained]; they live through the label stage
-	std::vector<std::pair<const char*, double>> host_marks;      // ... and the host timer's marks of that run, for recompress' own line
+	std::vector<std::pair<const char*, double>> host_marks;      // the host timer's marks of that run: read by ckl_recompress.hip's profile line (CKL_PROFILE), by nothing else
 	VolumeStats planes_stats;          // max / pairs of the volume the cached planes were built from
 	int64_t planes_dims[3] = { 0, 0, 0 };
 	std::vector<uint64_t> h_rbase;
@@ -194,6 +194,35 @@ inline void hand_out(const uint8_t* bytes, size_t n, OutAlloc how, uint8_t** out
 	*out_len = n;
 }
 inline void hand_out(const std::vector<uint8_t>& bin, OutAlloc how, uint8_t** out, uint64_t* out_len) { hand_out(bin.data(), bin.size(), how, out, out_len); }
+
+// the label planes of the session, V then H, as the kernels take them
+inline uint32_t* plane_v(const ckl_encoder& e) { return e.d_planes.p; }
+inline uint32_t* plane_h(const ckl_encoder& e, uint32_t ns) { return e.d_planes.p + e.plane_words * ns; }
+
+// what every entry point refuses before it asks for a device (ckl_encode.hip)
+void check_dims(int64_t sx, int64_t sy, int64_t sz, int dtype_bytes, int is_signed);
+// The stream's header as the volume's statistics decide it unless the overrides do; of an empty volume (all statistics 0)
+// it is the whole stream.  num_label_bytes comes later.
+Header stream_header(int data_width, int64_t sx, int64_t sy, int64_t sz, const VolumeStats& st, bool allow_pins, bool fortran_order, uint64_t markov_model_order, const ckl_encode_overrides* ov);
+inline std::vector<uint8_t> header_bytes(const Header& head) {
+	std::vector<uint8_t> hb;
+	head.write(hb);
+	return hb;
+}
+
+// Planes that the caller's own kernels write, not planes_pass (ckl_recompress.hip, reencode_markov).  planes_adopt: the
+// session takes their geometry and holds room for V | H (plane_v, plane_h) and for d_count_vh, [4][ns], whose first
+// count_rows rows are zeroed on the session's stream.  planes_adopt_counts, once the kernels ran: rows 0 and 1 of what
+// they left in d_count_vh, fetched by the caller, become the session's count_v and count_h.
+void planes_adopt(ckl_encoder& e, uint32_t row_words, uint64_t plane_words, uint32_t ns, uint32_t count_rows);
+void planes_adopt_counts(ckl_encoder& e, const std::vector<uint32_t>& counts, uint32_t ns);
+// The one door from a decode session's tables into the encoder: the stream of the volume whose planes and counts stand
+// adopted in the session, whose statistics are `st` and whose components take their labels from `labels`
+// (ckl_recompress.hpp).  FLAT labels, background colour chosen as compress() chooses it.  The session points at `labels`
+// for the length of the call only, however it ends.
+void encode_from_planes(
+	ckl_encoder& e, const dev::RunLabels& labels, int64_t sx, int64_t sy, int64_t sz, int data_width, bool fortran_order,
+	uint64_t markov_model_order, const VolumeStats& st, const std::vector<uint32_t>& counts, uint8_t** out, uint64_t* out_len);
 
 // The whole pin stage of a volume that one device holds (ckl_encode_pins.hip, instantiated there for the four label
 // widths): the pin label section from the labels, the component id of every voxel and the label of every component

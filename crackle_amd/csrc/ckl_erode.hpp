@@ -31,11 +31,6 @@ struct ErodeArgs {
 	uint32_t nslices;
 };
 
-// bits [x, end) of a word
-__device__ __forceinline__ uint32_t bits_from_to(uint32_t x, uint32_t end) {
-	return (end >= 32u ? 0xFFFFFFFFu : ((1u << end) - 1u)) & ~((1u << x) - 1u);
-}
-
 // run_label[rbase[zi] + run] = label of run `run` of slice zi.  grid = (any, nslices), grid-stride over the runs
 __global__ void __launch_bounds__(kBlock) k_erode_run_labels(RunLabels t, uint64_t* __restrict__ run_label) {
 	const uint32_t zi = blockIdx.y;
@@ -57,6 +52,29 @@ struct SliceRunLabels {
 	__device__ __forceinline__ SliceRunLabels(const RunLabels& t, const uint64_t* run_label, uint32_t zi) : lab(run_label + t.rbase[zi]), n(t.nruns[zi]) {}
 	__device__ __forceinline__ uint64_t operator()(uint32_t run) const { return n ? lab[run < n ? run : n - 1u] : 0ull; }
 };
+
+// One walk over the runs of word `p` of slice zi (b: its breaks), one label fetch per run.  Returns the bits of the
+// pixels whose label is not 0; same_as_before: bit x set where pixel x carries the label of the pixel before it in the
+// row (x = 0 of the row: set).  Bits at or past sx are 0 in both.  (k_dilate_nonzero has no use for the second word.)
+__device__ __forceinline__ uint32_t nonzero_bits(const RunLabels& t, const uint64_t* run_label, uint32_t zi, const PlaneWord& p, uint32_t b, uint32_t& same_as_before) {
+	const SliceRunLabels lab(t, run_label, zi);
+	uint32_t rc = t.word_base[p.at] - 1u;      // the run that reaches into the word from the left
+	uint64_t lc = p.w ? lab(rc) : 0ull;
+	uint32_t nz = 0, d = p.valid;
+	uint32_t rest = (b | 1u) & p.valid;
+	while (rest) {
+		const uint32_t x = __builtin_ctz(rest);
+		rest &= rest - 1u;
+		if ((b >> x) & 1u) {
+			const uint64_t l = lab(++rc);
+			if ((p.w | x) && l != lc) d &= ~(1u << x);
+			lc = l;
+		}
+		if (lc) nz |= bits_from_to(x, rest ? __builtin_ctz(rest) : 32u);
+	}
+	same_as_before = d;
+	return nz & p.valid;
+}
 
 // bit x set: pixel x of word w carries the same label in row (yc, zc) and in row (yn, zn).  The word is cut at the
 // breaks of both rows; inside a piece both rows have one label each.
@@ -91,32 +109,15 @@ __global__ void __launch_bounds__(kBlock) k_erode_terms(
 ) {
 	const RunGeom& g = t.g;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	if (i >= g.plane_words) return;
-	const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-	const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
-	const uint64_t at = zi * g.plane_words + i;
-	const uint32_t valid = g.valid_mask(w);
+	const PlaneWord pw(g, zi, i);
+	const uint32_t y = pw.y, w = pw.w, valid = pw.valid;
+	const uint64_t at = pw.at;
 	const uint32_t b = g.breaks(zi, y, w);
 	// the row itself: where the label is not 0, and where it equals the pixel before
-	uint32_t nz = 0, d = valid;
-	{
-		const SliceRunLabels lab(t, run_label, zi);
-		uint32_t rc = t.word_base[at] - 1u;
-		uint64_t lc = w ? lab(rc) : 0ull;
-		uint32_t rest = (b | 1u) & valid;
-		while (rest) {
-			const uint32_t x = __builtin_ctz(rest);
-			rest &= rest - 1u;
-			if ((b >> x) & 1u) {
-				const uint64_t l = lab(++rc);
-				if ((w | x) && l != lc) d &= ~(1u << x);
-				lc = l;
-			}
-			if (lc) nz |= bits_from_to(x, rest ? __builtin_ctz(rest) : 32u);
-		}
-		nz &= valid;
-	}
+	uint32_t d;
+	const uint32_t nz = nonzero_bits(t, run_label, zi, pw, b, d);
 	// the neighbour rows: k = 0 .. 3 the face rows, 4 .. 7 the diagonal ones
 	uint32_t q1 = nz, q2 = valid;
 	const uint32_t nrows = a.connectivity == 6u ? 4u : 8u;
@@ -148,13 +149,10 @@ __global__ void __launch_bounds__(kBlock) k_erode_keep(
 	__shared__ unsigned long long s_max[kWaves];
 	const RunGeom& g = t.g;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	unsigned long long mx = 0;
 	if (i < g.plane_words) {
-		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
-		const uint64_t at = zi * g.plane_words + i;
-		const uint32_t valid = g.valid_mask(w);
+		const auto [y, w, valid, at] = PlaneWord(g, zi, i);
 		const bool first = w == 0u, last = w + 1u == g.row_words;
 		const uint32_t d = planeD[at] | ~valid;
 		const uint32_t dn = last ? 0xFFFFFFFFu : planeD[at + 1];
@@ -186,13 +184,7 @@ __global__ void __launch_bounds__(kBlock) k_erode_keep(
 			}
 		}
 	}
-	for (int dd = kWave / 2; dd >= 1; dd >>= 1) { const unsigned long long o = __shfl_xor(mx, dd, kWave); mx = o > mx ? o : mx; }
-	if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		for (int wv = 1; wv < kWaves; wv++) mx = s_max[wv] > mx ? s_max[wv] : mx;
-		if (mx) atomicMax(max_out, mx);
-	}
+	block_max_into(mx, s_max, max_out);
 }
 
 // One thread per word: the eroded volume's planes V = K ^ K(x - 1) and H = K ^ K(y - 1), with the bits and the counts
@@ -207,13 +199,10 @@ __global__ void __launch_bounds__(kBlock) k_erode_planes(
 	__shared__ uint32_t s_red[kWaves];
 	const RunGeom& g = t.g;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	uint32_t nv = 0, nh = 0, nw = 0;
 	if (i < g.plane_words) {
-		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
-		const uint64_t at = zi * g.plane_words + i;
-		const uint32_t valid = g.valid_mask(w);
+		const auto [y, w, valid, at] = PlaneWord(g, zi, i);
 		const uint32_t k = keep[at];
 		const uint32_t kl = w ? keep[at - 1] : 0u;
 		uint32_t v = (k ^ ((k << 1) | (kl >> 31))) & valid;
@@ -229,12 +218,7 @@ __global__ void __launch_bounds__(kBlock) k_erode_planes(
 		planeV[at] = v; planeH[at] = h;
 		nv = __popc(v); nh = __popc(h);
 	}
-	nv = block_sum(nv, s_red); nh = block_sum(nh, s_red); nw = block_sum(nw, s_red);
-	if (threadIdx.x == 0) {
-		if (nv) atomicAdd(counts + zi, nv);
-		if (nh) atomicAdd(counts + nslices + zi, nh);
-		if (nw) atomicAdd(counts + 2u * nslices + zi, nw);
-	}
+	add_plane_counts(nv, nh, nw, s_red, counts, nslices, zi);
 }
 
 }  // namespace dev

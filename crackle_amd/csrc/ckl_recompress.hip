@@ -1,0 +1,238 @@
+// crackle.operations.recompress (crackle/operations.py:664-857 decodes slabs to voxels and compresses them again), and
+// erode and dilate, which are the same road with another volume at its end.  Here no voxel exists anywhere: a TABLES run
+// of the decoder leaves the runs of every slice and the label of every component, a plane stage writes the encoder's
+// planes and their counts from them (plain: ckl_recompress.hpp, eroded: ckl_erode.hpp, dilated: ckl_dilate.hpp), and
+// encode_from_planes (ckl_encoder.hpp) goes on as the encoder does from cached planes, with its label stage reading the
+// same tables.  The bytes are those of compress(edit(decompress(stream)), markov_model_order).
+#include "ckl_encoder.hpp"
+#include "ckl_decoder.hpp"
+#include "ckl_recompress.hpp"
+#include "ckl_erode.hpp"
+#include "ckl_dilate.hpp"
+
+#include <algorithm>
+#include <chrono>
+
+using namespace ckl;
+using namespace ckl::dev;
+
+namespace {
+
+// what a call does to the labels on their way through
+struct LabelEdit {
+	enum Kind { NONE, ERODE, DILATE } kind = NONE;
+	int connectivity = 0;          // ERODE, DILATE: 6, 18, 26
+	bool keep_border = false;      // ERODE: neighbours outside the volume are ignored
+};
+
+// per kind: the operation's name, and the two fields of its CKL_PROFILE line that carry the kind in their names
+struct EditNames { const char *op, *planes_field, *device_field; };
+constexpr EditNames kEditNames[] = {
+	{ "recompress", "label_planes", "k_label_planes_from_runs_device" },
+	{ "erode", "keep_planes", "k_erode_device" },
+	{ "dilate", "gain_planes", "k_dilate_device" },
+};
+
+// Device scratch of one call's edit.  What a plane stage returns points into it and is read by the encoder's label
+// stage: it lives to the end of the call.
+struct EditScratch {
+	DevBuf<uint32_t> erode_p_c_d_keep;         // ckl_erode.hpp's planes P | C | D | K, [nslices][plane_words] each
+	DevBuf<uint32_t> dilate_nonzero_gain;      // ckl_dilate.hpp's planes N | gain, [nslices][plane_words] each
+	DevBuf<uint64_t> dilate_gain_off;          // [nslices][plane_words]
+	DevBuf<uint64_t> dilate_gain_label;        // [gained]
+};
+
+// what the plane stages launch with
+struct Road {
+	ckl_decoder& d;                    // after its TABLES run
+	ckl_encoder& e;                    // planes_adopt() done: the stages write plane_v / plane_h and d_count_vh [3][ns]
+	hipStream_t s;                     // the encode session's
+	uint32_t ns;
+	dim3 word_grid;                    // a thread per 32-pixel word
+	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's cursor
+};
+
+// the decode session's tables as the kernels of this road read them
+RunLabels run_labels(const ckl_decoder& d) {
+	const RunArrays ra = run_arrays(d);
+	RunLabels src;
+	src.g = run_geom(d);
+	src.word_base = ra.word_base; src.rbase = ra.rbase; src.run_cc = ra.run_cc; src.nruns = ra.nruns;
+	src.comp_off = d.d_comp_off.p; src.ncomp = d.d_ncomp_expect.p; src.label_map = d.d_label_map.p;
+	return src;
+}
+
+// one label per run, at the runs' own bases (in PAINT's scratch of the decode session): what erode and dilate read
+const uint64_t* gather_run_labels(const Road& r, const RunLabels& src) {
+	r.d.d_run_label.ensure(r.d.rtot);
+	hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((r.d.max_rcap + kBlock - 1) / kBlock + 1, 256), r.ns), dim3(kBlock), 0, r.s, src, r.d.d_run_label.p);
+	return r.d.d_run_label.p;
+}
+
+// The three plane stages.  Each only launches; what the label stage needs beside the tables is what it hands back:
+// nothing, the keep plane, the gain triple.
+void plain_planes(const Road& r, const RunLabels& src) {
+	hipLaunchKernelGGL(k_label_planes_from_runs, r.word_grid, dim3(kBlock), 0, r.s, src, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
+}
+
+// returns the keep plane K; counters[0] takes the largest surviving label
+const uint32_t* eroded_planes(const Road& r, const RunLabels& src, const uint64_t* run_label, const LabelEdit& edit, EditScratch& scratch) {
+	const size_t pw = r.e.plane_words * r.ns;
+	scratch.erode_p_c_d_keep.ensure(4 * pw);
+	uint32_t *plane_p = scratch.erode_p_c_d_keep.p, *plane_c = plane_p + pw, *plane_d = plane_c + pw, *keep = plane_d + pw;
+	const ErodeArgs ea = { static_cast<uint32_t>(edit.connectivity), edit.keep_border ? 1u : 0u, r.ns };
+	hipLaunchKernelGGL(k_erode_terms, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, ea, plane_p, plane_c, plane_d);
+	hipLaunchKernelGGL(k_erode_keep, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, ea, plane_p, plane_c, plane_d, keep, r.counters);
+	hipLaunchKernelGGL(k_erode_planes, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, keep, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
+	return keep;
+}
+
+// returns the number of gained pixels and leaves the gain triple in src; 0: nothing was gained, the triple stays null and
+// the planes are the plain ones
+unsigned long long dilated_planes(const Road& r, RunLabels& src, const uint64_t* run_label, const LabelEdit& edit, EditScratch& scratch) {
+	const size_t pw = r.e.plane_words * r.ns;
+	scratch.dilate_nonzero_gain.ensure(2 * pw);
+	scratch.dilate_gain_off.ensure(pw);
+	uint32_t *plane_n = scratch.dilate_nonzero_gain.p, *gain = plane_n + pw;
+	const DilateArgs da = { static_cast<uint32_t>(edit.connectivity), r.ns };
+	hipLaunchKernelGGL(k_dilate_nonzero, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, plane_n);
+	hipLaunchKernelGGL(k_dilate_gain, r.word_grid, dim3(kBlock), 0, r.s, src.g, da, plane_n, gain, scratch.dilate_gain_off.p, r.counters + 1);
+	const unsigned long long gained = download(r.counters + 1, 1, r.s)[0];      // the host sizes the gained pixels' labels
+	if (!gained) { plain_planes(r, src); return 0; }
+	scratch.dilate_gain_label.ensure(gained);
+	hipLaunchKernelGGL(k_dilate_mode, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, da, plane_n, gain, scratch.dilate_gain_off.p, scratch.dilate_gain_label.p);
+	src.gain = gain; src.gain_off = scratch.dilate_gain_off.p; src.gain_label = scratch.dilate_gain_label.p;
+	hipLaunchKernelGGL(k_dilate_planes, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
+	return gained;
+}
+
+// lib::pixel_pairs (lib.hpp:249-256): equal neighbours in x-fastest order — inside the rows every pair that V does not
+// mark, and the wrap-arounds the plane writer counted.  counts: [3][ns] bits of V | bits of H | wrap pairs
+VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_label, int64_t sx, int64_t sy, uint32_t ns) {
+	VolumeStats st;
+	st.max_label = max_label;
+	for (uint32_t zi = 0; zi < ns; zi++) st.pairs += static_cast<uint64_t>(sx - 1) * sy - counts[zi] + counts[2 * static_cast<size_t>(ns) + zi];
+	return st;
+}
+
+// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the three operations read it)
+void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, const ckl_encoder& e, float ms_kernel, unsigned long long gained) {
+	double graph = 0, cracks = 0, labels = 0, assembly = 0;
+	for (const auto& m : e.host_marks) {
+		const std::string name = m.first;
+		if (name == "planes" || name == "graph") graph += m.second;
+		else if (name == "cracks") cracks += m.second;
+		else if (name == "assembly" || name == "codes_d2h") assembly += m.second;
+		else labels += m.second;      // f:*, flat, l:*, label_table, labels_d2h: the label side, on the host under the crack trail
+	}
+	const EditNames& names = kEditNames[edit.kind];
+	char tail[40] = "";
+	if (edit.kind == LabelEdit::DILATE) snprintf(tail, sizeof(tail), " gained=%llu", gained);
+	fprintf(stderr, "[ckl %s host ms] tables=%.2f %s=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f %s=%.3f%s\n",
+		names.op, ms_tables, names.planes_field, ms_planes, graph, cracks, labels, assembly, names.device_field, ms_kernel, tail);
+}
+
+// What the host refuses, before any device is asked for: the stream's header and the markov order of the output
+// (markov_order < 0: the stream's own).
+Header checked_header(const uint8_t* buf, uint64_t n, int markov_order, const LabelEdit& edit, uint64_t& order) {
+	if (edit.kind != LabelEdit::NONE && edit.connectivity != 6 && edit.connectivity != 18 && edit.connectivity != 26)
+		throw Error(CKL_ERR_ARG, std::string("crackle_amd: ") + kEditNames[edit.kind].op + ": connectivity must be 6, 18 or 26. Got: " + std::to_string(edit.connectivity));
+	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
+	const Header head = Header::parse(buf, n);
+	if (head.is_signed) throw Error(CKL_ERR_ARG, "Signed integer data types are not currently supported.");
+	order = markov_order < 0 ? static_cast<uint64_t>(head.markov_model_order) : static_cast<uint64_t>(markov_order);
+	if (order > 15) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order must be in [0, 15]");
+	check_dims(head.sx, head.sy, head.sz, head.data_width, 0);
+	return head;
+}
+
+// a decode session of the whole stream after its TABLES run (a damaged slice raises here, as for a decode)
+DecoderPtr tables_session(const uint8_t* buf, uint64_t n, int device) {
+	DecoderPtr dec;
+	const int rc = open_decoder(buf, n, 0, -1, device, dec);
+	if (rc != CKL_OK) throw Error(rc, ckl_last_error());
+	enter(dec.get());
+	decoder_run(*dec, { Goal::TABLES });
+	CKL_HIP(hipStreamSynchronize(dec->stream));
+	return dec;
+}
+
+using Clock = std::chrono::steady_clock;
+double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, const LabelEdit& edit, uint8_t** out, uint64_t* out_len) {
+	uint64_t order = 0;
+	const Header head = checked_header(buf, n, markov_order, edit, order);
+	const int64_t sx = head.sx, sy = head.sy, sz = head.sz;
+	if (head.voxels() == 0) {
+		hand_out(header_bytes(stream_header(head.data_width, sx, sy, sz, VolumeStats(), false, head.fortran_order, order, nullptr)), OutAlloc::MALLOC, out, out_len);
+		return;
+	}
+	select_device(device);      // (what came before needs none: refusals and streams without voxels are the host's)
+	const auto t_start = Clock::now();
+	const DecoderPtr dec = tables_session(buf, n, device);
+	ckl_decoder& d = *dec;
+	const auto t_tables = Clock::now();
+	RunLabels src = run_labels(d);
+
+	// the planes of the edited labels, in an encode session of this call
+	DevBuf<unsigned long long> counters;
+	EditScratch scratch;
+	ckl_encoder* raw = nullptr;
+	if (ckl_encoder_create(sx, sy, sz, head.data_width, device, &raw) != CKL_OK) throw Error(CKL_ERR_RUNTIME, ckl_last_error());
+	const EncoderPtr enc(raw);
+	ckl_encoder& e = *enc;
+	enter(&e);
+	const uint32_t ns = d.nslices;
+	planes_adopt(e, d.row_words, d.plane_words, ns, 3);
+	counters.ensure(2);
+	CKL_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), e.stream));
+	const Road r = { d, e, e.stream, ns, dim3(static_cast<uint32_t>((d.plane_words + kBlock - 1) / kBlock), ns), counters.p };
+	CKL_HIP(hipEventRecord(e.evd0, r.s));
+	const uint64_t* run_label = edit.kind == LabelEdit::NONE ? nullptr : gather_run_labels(r, src);
+	unsigned long long gained = 0;
+	if (edit.kind == LabelEdit::ERODE) src.keep = eroded_planes(r, src, run_label, edit, scratch);
+	else if (edit.kind == LabelEdit::DILATE) gained = dilated_planes(r, src, run_label, edit, scratch);
+	else plain_planes(r, src);
+	CKL_HIP(hipEventRecord(e.evd1, r.s));
+	// (k_erode_keep has taken the largest surviving label; dilation leaves the largest label what it was)
+	if (edit.kind != LabelEdit::ERODE) hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, r.s,
+		d.d_label_map.p, d.total_comp, counters.p);
+	const std::vector<uint32_t> counts = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), r.s);
+	const VolumeStats st = stats_from_counts(counts, download(counters.p, 1, r.s)[0], sx, sy, ns);
+	float ms_kernel = 0.f;
+	CKL_HIP(hipEventElapsedTime(&ms_kernel, e.evd0, e.evd1));
+	const auto t_planes = Clock::now();
+
+	encode_from_planes(e, src, sx, sy, sz, head.data_width, head.fortran_order, order, st, counts, out, out_len);
+	if (getenv("CKL_PROFILE")) print_profile(edit, ms_between(t_start, t_tables), ms_between(t_tables, t_planes), e, ms_kernel, gained);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ckl_recompress(const uint8_t* buf, uint64_t n, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		recompress(buf, n, markov_model_order, device, LabelEdit(), out, out_len);
+	});
+}
+
+int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		if (flags & ~CKL_ERODE_KEEP_BORDER) throw Error(CKL_ERR_ARG, "crackle_amd: erode: unknown flags");
+		recompress(buf, n, markov_model_order, device, { LabelEdit::ERODE, connectivity, (flags & CKL_ERODE_KEEP_BORDER) != 0 }, out, out_len);
+	});
+}
+
+int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: dilate: flags must be 0");
+		recompress(buf, n, markov_model_order, device, { LabelEdit::DILATE, connectivity, false }, out, out_len);
+	});
+}
+
+}  // extern "C"

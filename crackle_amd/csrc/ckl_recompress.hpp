@@ -7,6 +7,8 @@
 //   k_label_map_max                lib::max_label (lib.hpp:224-247): every component has a pixel
 //   k_component_labels_from_runs   the label of every component of the NEW planes, from its first pixel
 //                                  (what k_mapping_comps and k_slice_resolve_enc read from the volume)
+// The first two are launched by the road itself (ckl_recompress.hip), the third by the encoder's label stage
+// (ckl_encode.hip): two units see this header, so its kernels are static.
 #pragma once
 
 #include "ckl_run_types.hpp"
@@ -31,13 +33,24 @@ struct RunLabels {
 	const uint64_t* gain_off = nullptr;
 	const uint64_t* gain_label = nullptr;
 
-	// label of run `run` of slice zi; everything read from the tables is clamped as k_paint_window clamps it
-	__device__ __forceinline__ uint64_t label_of(uint32_t zi, uint32_t run) const {
+	// the labels of one slice's runs, the slice's bases fetched once; everything read from the tables is clamped as
+	// k_paint_window clamps it
+	struct Slice {
+		const uint32_t* rcc;
+		const uint64_t* lmap;
+		uint32_t n, last, nce;      // runs of the slice, its last run (0 without any), components
+		__device__ __forceinline__ uint64_t operator()(uint32_t run) const {
+			if (!n) return 0ull;
+			const uint32_t cc = rcc[run < last ? run : last];
+			return cc < nce ? lmap[cc] : 0ull;
+		}
+	};
+	__device__ __forceinline__ Slice slice(uint32_t zi) const {
 		const uint32_t n = nruns[zi];
-		if (!n) return 0ull;
-		const uint32_t cc = run_cc[rbase[zi] + (run < n ? run : n - 1u)];
-		return cc < ncomp[zi] ? label_map[comp_off[zi] + cc] : 0ull;
+		return { run_cc + rbase[zi], label_map + comp_off[zi], n, n ? n - 1u : 0u, ncomp[zi] };
 	}
+	// label of run `run` of slice zi
+	__device__ __forceinline__ uint64_t label_of(uint32_t zi, uint32_t run) const { return slice(zi)(run); }
 	// true, and the label in l: pixel (x, y) of slice zi is a gained one
 	__device__ __forceinline__ bool gained(uint32_t zi, uint32_t x, uint32_t y, uint64_t& l) const {
 		if (!gain) return false;
@@ -54,6 +67,17 @@ struct RunLabels {
 	}
 };
 
+// The tail of the three plane writers (here, ckl_erode.hpp, ckl_dilate.hpp): a thread's bits of V, bits of H and wrap
+// pairs, summed over the workgroup, into slice zi's entries of counts [3][nslices].  Every thread of the workgroup calls it.
+__device__ __forceinline__ void add_plane_counts(uint32_t nv, uint32_t nh, uint32_t nw, uint32_t* s_red, uint32_t* counts, uint32_t nslices, uint32_t zi) {
+	nv = block_sum(nv, s_red); nh = block_sum(nh, s_red); nw = block_sum(nw, s_red);
+	if (threadIdx.x == 0) {
+		if (nv) atomicAdd(counts + zi, nv);
+		if (nh) atomicAdd(counts + nslices + zi, nh);
+		if (nw) atomicAdd(counts + 2u * nslices + zi, nw);
+	}
+}
+
 // One thread per 32-pixel word (zi, y, w).  The runs of a word are consecutive, word_base + k for its k-th break,
 // so a thread fetches one label per run, not per pixel.
 //   V: bit x (1 <= x < sx) where a run starts at x and its label differs from the run before it.
@@ -64,29 +88,17 @@ struct RunLabels {
 // counts (zeroed by the host): [nslices] bits of V, [nslices] bits of H, [nslices] wrap pairs — the first pixel of
 // a row equal to the pixel before it in x-fastest order (the last of the row above, or of the slice before).
 // grid = (ceil(plane_words / 256), nslices)
-__global__ void __launch_bounds__(kBlock) k_label_planes_from_runs(
+static __global__ void __launch_bounds__(kBlock) k_label_planes_from_runs(
 	RunLabels t, uint32_t* __restrict__ planeV, uint32_t* __restrict__ planeH, uint32_t* __restrict__ counts, uint32_t nslices
 ) {
 	__shared__ uint32_t s_red[kWaves];
 	const RunGeom& g = t.g;
 	const uint32_t zi = blockIdx.y;
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+	const uint64_t i = this_word();
 	uint32_t nv = 0, nh = 0, nw = 0;
 	if (i < g.plane_words) {
-		const uint32_t y = static_cast<uint32_t>(i / g.row_words);
-		const uint32_t w = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words);
-		const uint32_t n = t.nruns[zi];
-		const uint32_t last = n ? n - 1u : 0u;
-		const uint32_t nce = t.ncomp[zi];
-		const uint32_t* rcc = t.run_cc + t.rbase[zi];
-		const uint64_t* lmap = t.label_map + t.comp_off[zi];
-		auto label_of = [&](uint32_t run) -> uint64_t {
-			if (!n) return 0ull;
-			const uint32_t cc = rcc[run < last ? run : last];
-			return cc < nce ? lmap[cc] : 0ull;
-		};
-		const uint64_t at = zi * g.plane_words + i;
-		const uint32_t valid = g.valid_mask(w);
+		const auto [y, w, valid, at] = PlaneWord(g, zi, i);
+		const RunLabels::Slice label_of = t.slice(zi);
 		const uint32_t b = g.breaks(zi, y, w);
 		const uint32_t bu = y ? g.breaks(zi, y - 1u, w) : 0u;
 		uint32_t rc = t.word_base[at] - 1u;                                // the run that reaches into the word from the left
@@ -113,26 +125,18 @@ __global__ void __launch_bounds__(kBlock) k_label_planes_from_runs(
 			}
 			if (y) {
 				if ((bu >> x) & 1u) lu = label_of(++ru);
-				if (lc != lu) {
-					const uint32_t end = rest ? __builtin_ctz(rest) : 32u;      // the piece is [x, end)
-					h |= (end >= 32u ? 0xFFFFFFFFu : ((1u << end) - 1u)) & ~((1u << x) - 1u);
-				}
+				if (lc != lu) h |= bits_from_to(x, rest ? __builtin_ctz(rest) : 32u);      // the piece ends at the next cut
 			}
 		}
 		h &= valid;
 		planeV[at] = v; planeH[at] = h;
 		nv = __popc(v); nh = __popc(h);
 	}
-	nv = block_sum(nv, s_red); nh = block_sum(nh, s_red); nw = block_sum(nw, s_red);
-	if (threadIdx.x == 0) {
-		if (nv) atomicAdd(counts + zi, nv);
-		if (nh) atomicAdd(counts + nslices + zi, nh);
-		if (nw) atomicAdd(counts + 2u * nslices + zi, nw);
-	}
+	add_plane_counts(nv, nh, nw, s_red, counts, nslices, zi);
 }
 
 // the largest entry of the component -> label map; *out zeroed by the host
-__global__ void __launch_bounds__(kBlock) k_label_map_max(const uint64_t* __restrict__ label_map, uint64_t n, unsigned long long* __restrict__ out) {
+static __global__ void __launch_bounds__(kBlock) k_label_map_max(const uint64_t* __restrict__ label_map, uint64_t n, unsigned long long* __restrict__ out) {
 	__shared__ unsigned long long s_max[kWaves];
 	unsigned long long mx = 0;
 	const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
@@ -140,19 +144,13 @@ __global__ void __launch_bounds__(kBlock) k_label_map_max(const uint64_t* __rest
 		const unsigned long long v = label_map[i];
 		mx = v > mx ? v : mx;
 	}
-	for (int d = kWave / 2; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(mx, d, kWave); mx = o > mx ? o : mx; }
-	if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		for (int w = 1; w < kWaves; w++) mx = s_max[w] > mx ? s_max[w] : mx;
-		if (mx) atomicMax(out, mx);
-	}
+	block_max_into(mx, s_max, out);
 }
 
 // One thread per component of the NEW planes: its first pixel (the strip path leaves it in the resolve's slots, the
 // run pipeline in comp_pix) -> the decoder's run at that pixel -> its label.  ncomp / comp_off / rbase_enc are the
 // ENCODER's.  grid = (ceil(most components of a slice / 256), nslices)
-__global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
+static __global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
 	RunLabels t, const uint64_t* __restrict__ slots, uint32_t slot_cap, const uint32_t* __restrict__ comp_pix, const uint64_t* __restrict__ rbase_enc,
 	const uint32_t* __restrict__ ncomp, const uint64_t* __restrict__ comp_off, uint64_t* __restrict__ mapping
 ) {

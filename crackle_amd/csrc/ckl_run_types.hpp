@@ -58,6 +58,20 @@ struct RunGeom {
 	__device__ __forceinline__ uint32_t ups_of(uint32_t h, uint32_t w) const { return (flip ? ~h : h) & valid_mask(w); }
 };
 __device__ __forceinline__ uint32_t mask_le(uint32_t bit) { return bit >= 31u ? 0xFFFFFFFFu : ((2u << bit) - 1u); }
+// bits [x, end) of a word
+__device__ __forceinline__ uint32_t bits_from_to(uint32_t x, uint32_t end) {
+	return (end >= 32u ? 0xFFFFFFFFu : ((1u << end) - 1u)) & ~((1u << x) - 1u);
+}
+
+// The 32-pixel word i (< plane_words) of slice zi: its row, its place in the row, its index in an [nslices][plane_words]
+// array and its pixels inside the row.  this_word(): the word of a thread in a grid of (ceil(plane_words / 256), nslices).
+__device__ __forceinline__ uint64_t this_word() { return static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; }
+struct PlaneWord {
+	uint32_t y, w, valid;
+	uint64_t at;
+	__device__ __forceinline__ PlaneWord(const RunGeom& g, uint32_t zi, uint64_t i)
+		: y(static_cast<uint32_t>(i / g.row_words)), w(static_cast<uint32_t>(i - static_cast<uint64_t>(y) * g.row_words)), valid(g.valid_mask(w)), at(zi * g.plane_words + i) {}
+};
 
 struct RunArrays {
 	uint32_t* word_base;       // [nslices][plane_words]

@@ -22,6 +22,32 @@ def _take(out: C.c_void_p, n: C.c_uint64) -> bytes:
     _lib.lib().ckl_free(out)
 
 
+def _checked_connectivity(what: str, connectivity: int) -> None:
+  if connectivity not in (6, 18, 26):
+    raise ValueError(f"{what}: connectivity must be 6, 18 or 26. Got: {connectivity}")
+
+
+def _checked_order(what: str, markov_model_order: Optional[int]) -> None:
+  if markov_model_order is not None and int(markov_model_order) < 0:
+    raise ValueError(f"{what}: markov_model_order must not be negative. Got: {int(markov_model_order)}")
+
+
+def _reencode(what: str, entry: str, binary: bytes, edit_args: tuple, markov_model_order: Optional[int], device: int) -> bytes:
+  """The call that recompress, erode and dilate share: `entry` is the library's function, which takes the stream,
+  the operation's own arguments, the order (-1: the stream's own), the device and the output pair."""
+  from .codec import _raise
+  b = bytes(binary)
+  if header(b).signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  _checked_order(what, markov_model_order)
+  order = -1 if markov_model_order is None else int(markov_model_order)
+  out, n = C.c_void_p(), C.c_uint64()
+  rc = getattr(_lib.lib(), entry)(b, len(b), *edit_args, order, int(device), C.byref(out), C.byref(n))
+  if rc != _lib.CKL_OK:
+    _raise(rc)
+  return _take(out, n)
+
+
 def zstack(images: Sequence[bytes]) -> bytes:
   """Concatenates the streams of consecutive z-slabs into the stream of the whole volume
   (crackle/operations.py:424-548); byte-identical to compress() of the whole when the slabs
@@ -348,8 +374,7 @@ def connected_components(
   slabs.  binary_image=True (all nonzero voxels one foreground) merges different labels, which
   removes cracks and needs a re-encode: ValueError.  Format version 0 streams carry no crack crcs:
   ValueError.  FLAT and pin label streams are accepted."""
-  if connectivity not in (6, 18, 26):
-    raise ValueError(f"connected_components: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  _checked_connectivity("connected_components", connectivity)
   if binary_image:
     raise ValueError(
       "connected_components: binary_image=True is not supported: merging different labels removes "
@@ -420,8 +445,7 @@ def dust(
   6, 18 or 26 ValueError.  The stream of an empty volume is returned as it is, without a device.  A damaged slice
   raises what decompress raises for it."""
   from .codec import _raise
-  if connectivity not in (6, 18, 26):
-    raise ValueError(f"dust: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  _checked_connectivity("dust", connectivity)
   threshold = int(threshold)
   if threshold < 0:
     raise ValueError(f"dust: threshold must not be negative. Got: {threshold}")
@@ -476,8 +500,7 @@ def fill_holes(binary: bytes, connectivity: int = 6, return_filled: bool = False
   per-label filling that swallows enclosed foreign labels (fastmorph's remove_enclosed), z-ranges, a sharded
   version."""
   from .codec import _raise
-  if connectivity not in (6, 18, 26):
-    raise ValueError(f"fill_holes: connectivity must be 6, 18 or 26. Got: {connectivity}")
+  _checked_connectivity("fill_holes", connectivity)
   b = bytes(binary)
   head = header(b)
   if head.format_version == 0:
@@ -625,20 +648,9 @@ def recompress(
   (ckl_recompress).  memory_target is accepted and ignored: there are no slabs.  allow_pins=True raises ValueError
   (pins need the voxel columns), signed streams TypeError as compress does; a damaged slice raises what
   decompress raises for it."""
-  from .codec import _raise
   if allow_pins:
     raise ValueError("recompress: allow_pins is not supported: pins are found along the voxel columns, which are never decoded here.")
-  b = bytes(binary)
-  if header(b).signed:
-    raise TypeError("Signed integer data types are not currently supported.")
-  order = -1 if markov_model_order is None else int(markov_model_order)
-  if markov_model_order is not None and order < 0:
-    raise ValueError(f"recompress: markov_model_order must not be negative. Got: {order}")
-  out, n = C.c_void_p(), C.c_uint64()
-  rc = _lib.lib().ckl_recompress(b, len(b), order, int(device), C.byref(out), C.byref(n))
-  if rc != _lib.CKL_OK:
-    _raise(rc)
-  return _take(out, n)
+  return _reencode("recompress", "ckl_recompress", binary, (), markov_model_order, device)
 
 
 def erode(
@@ -663,21 +675,9 @@ def erode(
   row, and the encoder's crack and label stages follow as for recompress (ckl_erode).  Signed streams raise
   TypeError, a bad connectivity or a negative order ValueError; a damaged slice raises what decompress raises for
   it; the stream of an empty volume comes back as recompress returns it, without a device."""
-  from .codec import _raise
-  if connectivity not in (6, 18, 26):
-    raise ValueError(f"erode: connectivity must be 6, 18 or 26. Got: {connectivity}")
-  b = bytes(binary)
-  if header(b).signed:
-    raise TypeError("Signed integer data types are not currently supported.")
-  order = -1 if markov_model_order is None else int(markov_model_order)
-  if markov_model_order is not None and order < 0:
-    raise ValueError(f"erode: markov_model_order must not be negative. Got: {order}")
+  _checked_connectivity("erode", connectivity)
   flags = 0 if erode_border else _lib.CKL_ERODE_KEEP_BORDER
-  out, n = C.c_void_p(), C.c_uint64()
-  rc = _lib.lib().ckl_erode(b, len(b), int(connectivity), flags, order, int(device), C.byref(out), C.byref(n))
-  if rc != _lib.CKL_OK:
-    _raise(rc)
-  return _take(out, n)
+  return _reencode("erode", "ckl_erode", binary, (int(connectivity), flags), markov_model_order, device)
 
 
 def dilate(
@@ -712,25 +712,8 @@ def dilate(
   Not done: background_only=False (every voxel takes its neighbourhood's mode), grey-level dilation, several
   iterations in one call, fused opening or closing, z-ranges, a sharded version, dilate in the stream-kind test
   matrix."""
-  from .codec import _raise
-  if connectivity not in (6, 18, 26):
-    raise ValueError(f"dilate: connectivity must be 6, 18 or 26. Got: {connectivity}")
-  b = bytes(binary)
-  if header(b).signed:
-    raise TypeError("Signed integer data types are not currently supported.")
-  order = -1 if markov_model_order is None else int(markov_model_order)
-  if markov_model_order is not None and order < 0:
-    raise ValueError(f"dilate: markov_model_order must not be negative. Got: {order}")
-  out, n = C.c_void_p(), C.c_uint64()
-  rc = _lib.lib().ckl_dilate(b, len(b), int(connectivity), 0, order, int(device), C.byref(out), C.byref(n))
-  if rc != _lib.CKL_OK:
-    _raise(rc)
-  return _take(out, n)
-
-
-def _checked_order(what: str, markov_model_order: Optional[int]) -> None:
-  if markov_model_order is not None and int(markov_model_order) < 0:
-    raise ValueError(f"{what}: markov_model_order must not be negative. Got: {int(markov_model_order)}")
+  _checked_connectivity("dilate", connectivity)
+  return _reencode("dilate", "ckl_dilate", binary, (int(connectivity), 0), markov_model_order, device)
 
 
 def opening(

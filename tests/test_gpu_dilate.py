@@ -1,6 +1,6 @@
 """GPU tests of crackle_amd.dilate (ckl_dilate: the decoder's run tables -> k_erode_run_labels, k_dilate_nonzero,
 k_dilate_gain, k_dilate_mode, k_dilate_planes -> the encoder's crack and label stages; crackle_amd/csrc/ckl_dilate.hpp
-and ckl_encode.hip), and of opening and closing on top of it.
+and ckl_recompress.hip), and of opening and closing on top of it.
 
 The check throughout: dilate(stream, ...) equals the checker's compress of the restated dilation (tests/dilate_numpy.py,
 worked from the INPUT array) byte for byte under the requested markov order (default: the stream's); the result

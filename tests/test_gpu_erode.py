@@ -1,6 +1,6 @@
 """GPU tests of crackle_amd.erode (ckl_erode: the decoder's run tables -> k_erode_run_labels, k_erode_terms,
 k_erode_keep, k_erode_planes -> the encoder's crack and label stages; crackle_amd/csrc/ckl_erode.hpp and
-ckl_encode.hip).
+ckl_recompress.hip).
 
 The check throughout: erode(stream, ...) equals the checker's compress of the restated erosion (tests/erode_numpy.py,
 worked from the INPUT array) byte for byte under the requested markov order (default: the stream's); the result

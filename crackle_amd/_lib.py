@@ -106,6 +106,7 @@ EXPORTS = {
   "ckl_encoder_walk_step_kinds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
   "ckl_encoder_last_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
   "ckl_encoder_walk_paths": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+  "ckl_encoder_emit_path": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
   "ckl_encoder_destroy": (None, [C.c_void_p]),
   "ckl_pin_labels_host": (C.c_int, [
     C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,

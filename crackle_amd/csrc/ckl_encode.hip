@@ -17,6 +17,7 @@
 #include "ckl_runs.hpp"
 #include "ckl_strips.hpp"
 #include "ckl_trail.hpp"
+#include "ckl_code_words.hpp"
 #include "ckl_recompress.hpp"
 
 #include <algorithm>
@@ -486,7 +487,9 @@ __global__ void __launch_bounds__(kFinishBlock) k_finish(FinishArgs a) {
 	__syncthreads();
 	__threadfence_block();
 
-	// ---- phase 2: compaction of tombstones + scatter of each chain to its sorted place ----
+	// ---- phase 2: scatter of each chain to its sorted place.  A permutation of chains: no kernel writes CODE_TOMB any
+	// more (k_trail_items lets the vanishing 'b' / 't' pairs vanish before a code exists, n_valid = n_raw), the
+	// compaction below finds nothing to compact ----
 	constexpr uint32_t kPer = 16;
 	uint32_t carry = 0;
 	for (uint32_t tile = 0; tile < nraw; tile += kFinishBlock * kPer) {
@@ -600,6 +603,287 @@ __global__ void __launch_bounds__(kFinishBlock) k_finish(FinishArgs a) {
 			else for (uint32_t k = 4u * w; k < nbytes; k++) out[k] = static_cast<uint8_t>(enc >> (8u * (k - 4u * w)));
 		}
 		if (tid == 0) a.payload_len[zi] = nbytes;
+	}
+}
+
+// ------------------------------------------------------------------------------
+// k_trail_emit: k_trail_offsets + k_trail_expand + k_finish in one workgroup per slice, the code points packed in LDS.
+// The three kernels move every code point through HBM three times as a byte (expanded, permuted, read for the
+// difference) although it exists packed beside its dart and every chain's final place is known before the first code
+// point is expanded.  Here an item ORs its code points, 2 bits each, into a buffer of words in LDS at their FINAL
+// index; the difference code is taken on the words (ckl_code_words.hpp) and the words are stored.  No workgroup waits
+// for another.
+//
+// Dynamic LDS, in words: item0[tcap] | dst[tcap] | words[wcap], where the chain tables that only the chain phase
+// reads (node, order, vstart: 3 tcap words) lie over the beginning of words[] until the words are zeroed.  A slice with
+// more than tcap chains keeps its chain tables in global memory (as k_finish does above kFinishChains); a slice with
+// more than 16 wcap code points — the host sizes wcap from an estimate, emit_plan — is emitted in windows of wcap
+// words, every item looking at every window.
+// ------------------------------------------------------------------------------
+constexpr int kEmitBlock = 1024;
+constexpr int kEmitWaves = kEmitBlock / kWave;
+constexpr uint32_t kEmitLong = 1024;      // segments to walk that the workgroup lists; a slice with more has them walked by the threads that meet them
+
+// what k_trail_emit does behind the offsets, on chain tables in LDS (a slice of up to tcap chains) or in global memory: the
+// caller hands the tables over so that each instance addresses its own memory (a pointer that may be either costs a flat
+// access, which waits for the loads in flight as well)
+struct EmitSlice {
+	uint32_t zi, n, nch, total, wcap;
+	const uint32_t* items;
+	const uint32_t* off;
+	const uint32_t* dlen;
+	uint64_t nb;
+};
+
+__device__ __forceinline__ void emit_chains_and_codes(
+	const TrailArgs& a, const FinishArgs& f, const EmitSlice& sl, uint32_t* words,
+	const uint32_t* ch_node, const uint32_t* item0, const uint32_t* vstart, uint32_t* order, uint32_t* dst,
+	const uint32_t* s_long, const uint32_t* s_nlong, uint32_t* s_carry
+) {
+	const uint32_t tid = threadIdx.x;
+	const uint32_t zi = sl.zi, n = sl.n, nch = sl.nch, total = sl.total;
+	const uint32_t sxe = f.sx + 1;
+
+	// ---- chains (k_finish phase 1, serial over chains): order by start vertex, output offsets, BOC index ----
+	if (tid == 0) {
+		auto clen = [&](uint32_t c) -> uint32_t { return (c + 1 < nch ? vstart[c + 1] : total) - vstart[c]; };
+		// chains come out in ascending raw start order and remove_initial_branch only
+		// moves a start inside its own component: insertion sort on a nearly sorted list
+		for (uint32_t c = 0; c < nch; c++) {
+			const uint32_t key = ch_node[c];
+			uint32_t p = c;
+			while (p > 0 && ch_node[order[p - 1]] > key) { order[p] = order[p - 1]; p--; }
+			order[p] = c;
+		}
+		uint32_t d = 0;
+		for (uint32_t i = 0; i < nch; i++) { dst[order[i]] = d; d += clen(order[i]); }
+
+		// write_boc_index (crackcodes.hpp:318-372)
+		uint8_t* b = f.boc + f.bbase[zi];
+		uint32_t num_y = 0, index_size = f.yw;
+		for (uint32_t i = 0; i < nch;) {
+			const uint32_t y = ch_node[order[i]] / sxe;
+			uint32_t j = i;
+			while (j < nch && ch_node[order[j]] / sxe == y) j++;
+			index_size += f.yw + (j - i + 1) * f.xw;
+			num_y++;
+			i = j;
+		}
+		uint32_t idx = 0;
+		put_le_dev(b + idx, index_size, 4); idx += 4;
+		put_le_dev(b + idx, num_y, f.yw); idx += f.yw;
+		uint32_t last_y = 0;
+		for (uint32_t i = 0; i < nch;) {
+			const uint32_t y = ch_node[order[i]] / sxe;
+			uint32_t j = i;
+			while (j < nch && ch_node[order[j]] / sxe == y) j++;
+			put_le_dev(b + idx, y - last_y, f.yw); idx += f.yw;
+			last_y = y;
+			put_le_dev(b + idx, j - i, f.xw); idx += f.xw;
+			uint32_t last_x = 0;
+			for (uint32_t k = i; k < j; k++) {
+				const uint32_t x = ch_node[order[k]] - sxe * y;
+				put_le_dev(b + idx, x - last_x, f.xw); idx += f.xw;
+				last_x = x;
+			}
+			i = j;
+		}
+		f.boc_len[zi] = idx;
+		a.n_raw[zi] = total; a.n_valid[zi] = total;
+		*s_carry = 0;
+	}
+	__syncthreads();
+	__threadfence_block();
+	// an item's code points move by dst - vstart of its chain (wrapping)
+	for (uint32_t c = tid; c < nch; c += kEmitBlock) dst[c] -= vstart[c];
+	__syncthreads();
+	__threadfence_block();
+
+	// ---- expansion to the final place, difference code, store: in windows of wcap words
+	const uint32_t nwords = (total + 15u) >> 4, nbytes = (total + 3u) >> 2;
+	const uint4* adjm = a.adjm + zi * a.adjm_stride;
+	uint8_t* out = f.payload + f.pbase[zi];        // 4-byte aligned
+	uint8_t* dcode = f.dcode + a.cbase[zi];        // 16-byte aligned (crack_pass rounds the capacities)
+	// the segments to walk stand in the list unless there were too many for it: then whoever meets one walks it.  The
+	// walks last as long as the longest segment, so the list's first wavefronts do nothing else and the others share
+	// the rest of the items
+	const uint32_t nl = *s_nlong;
+	const bool listed = nl <= kEmitLong;
+	const uint32_t walkers = listed ? min((nl + kWave - 1u) / kWave, static_cast<uint32_t>(kEmitWaves / 2)) * kWave : 0u;      // threads, whole wavefronts
+	for (uint32_t w0 = 0; w0 < nwords; w0 += sl.wcap) {
+		const uint32_t wn = min(sl.wcap, nwords - w0);
+		for (uint32_t i = tid; i < wn; i += kEmitBlock) words[i] = 0u;
+		__syncthreads();
+		auto or_word = [&](uint32_t gw, uint32_t v) {
+			const uint32_t wi = gw - w0;
+			if (v && wi < wn) atomicOr(words + wi, v);
+		};
+		// where item i begins: its raw offset moved with its chain, the last chain that begins at or in front of it (empty
+		// chains share their successor's first item)
+		auto place = [&](uint32_t i) -> uint32_t {
+			uint32_t lo = 0, hi = nch;
+			while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (item0[mid] <= i) lo = mid; else hi = mid; }
+			return sl.off[i] + dst[lo];
+		};
+		auto outside = [&](uint32_t p, uint32_t len) -> bool { return (p >> 4) >= w0 + wn || ((p + len - 1u) >> 4) < w0; };
+		// a segment too long for its dart's 16 bytes, a loop, the half of a split segment: walked again from its node,
+		// 16 code points collected per word
+		auto walk = [&](uint32_t d, uint32_t p, uint32_t len) {
+			const uint32_t v0 = a.node_vertex[sl.nb + (d >> 2)];
+			uint32_t y = v0 / a.sxe, x = v0 - y * a.sxe, k = d & 3u, acc = 0u;
+			MicroTile c;
+			c.lo = c.hi = make_uint4(0, 0, 0, 0); c.mx = c.my = 0xFFFFFFFFu;
+			for (uint32_t s = 0; s < len; s++) {
+				const uint32_t g = p + s;
+				acc |= trail_code(k) << (2u * (g & 15u));
+				if ((g & 15u) == 15u || s + 1u == len) { or_word(g >> 4, acc); acc = 0u; }
+				trail_step(x, y, k);
+				if (s + 1u == len) break;
+				// (a walk never leaves the graph, whose micro-tiles end there; one that would has not written its segment: the
+				// slice says so, k_code_offsets reports it and the run ends with the walk's overflow error)
+				if (x > a.sx || y > a.sy) { atomicOr(a.slice_err + zi, TRAIL_ERR_CAPACITY); break; }
+				if (!c.holds(x, y)) mt_load(c, adjm, x, y, a.mtx2);
+				k = (__ffs(c.nib(x, y) & ~(1u << (k ^ 1u))) - 1) & 3u;
+			}
+		};
+		if (tid < walkers) {
+			for (uint32_t j = tid; j < nl; j += walkers) {
+				const uint32_t i = s_long[j];
+				const uint32_t d = sl.items[i] & ~kItemMask, len = sl.dlen[d], p = place(i);
+				if (!outside(p, len)) walk(d, p, len);
+			}
+		}
+		else {
+			for (uint32_t i = tid - walkers; i < n; i += kEmitBlock - walkers) {
+				const uint32_t it = sl.items[i], kind = it & kItemMask;
+				if (kind != kItemSeg && kind != kItemCtl) continue;
+				const uint32_t p = place(i);
+				if (kind == kItemCtl) { or_word(p >> 4, (it & 3u) << (2u * (p & 15u))); or_word((p + 1u) >> 4, ((it >> 2) & 3u) << (2u * ((p + 1u) & 15u))); continue; }
+				const uint32_t d = it & ~kItemMask;
+				const uint32_t len = sl.dlen[d];
+				if (len == 0u || outside(p, len)) continue;
+				if (len <= kInlineCodes && a.dart_inline[sl.nb * 4u + d]) {
+					const uint4 q4 = a.dart_codes[sl.nb * 4u + d];
+					const uint32_t q[4] = { q4.x, q4.y, q4.z, q4.w };
+					uint32_t o[5];
+					const uint32_t gw = place_codes128(q, len, p, o);
+#pragma unroll
+					for (uint32_t j = 0; j < 5; j++) or_word(gw + j, o[j]);
+				}
+				else if (!listed) walk(d, p, len);
+			}
+		}
+		__syncthreads();
+		// whole-slice mod-4 difference code on the words (the code in front of the slice's first is 0), then the store
+		for (uint32_t i = tid; i < wn; i += kEmitBlock) {
+			const uint32_t gw = w0 + i;
+			uint32_t enc = packed_code_diff(words[i], i ? words[i - 1] >> 30 : *s_carry);
+			if (gw == nwords - 1u && (total & 15u)) enc &= (1u << (2u * (total & 15u))) - 1u;
+			if (f.markov) {
+				// one byte per difference code for k_markov_hist / k_markov_pack (bytes behind the last code: 0)
+				auto spread = [](uint32_t b) -> uint32_t { uint32_t x = (b | (b << 12)) & 0x000F000Fu; return (x | (x << 6)) & 0x03030303u; };
+				*reinterpret_cast<uint4*>(dcode + 16ull * gw) = make_uint4(spread(enc & 255u), spread((enc >> 8) & 255u), spread((enc >> 16) & 255u), spread(enc >> 24));
+			}
+			else if (4u * gw + 4u <= nbytes) reinterpret_cast<uint32_t*>(out)[gw] = enc;
+			else for (uint32_t k = 4u * gw; k < nbytes; k++) out[k] = static_cast<uint8_t>(enc >> (8u * (k - 4u * gw)));
+		}
+		__syncthreads();
+		if (tid == 0) *s_carry = words[wn - 1u] >> 30;
+		__syncthreads();
+	}
+	if (tid == 0) f.payload_len[zi] = f.markov ? 0u : nbytes;
+}
+
+// (eight wavefronts per SIMD: two workgroups share a CU only while the registers stay within that)
+__global__ void __launch_bounds__(kEmitBlock, 8) k_trail_emit(TrailArgs a, FinishArgs f, uint32_t tcap, uint32_t wcap) {
+	extern __shared__ uint32_t s_emit[];
+	__shared__ uint32_t s_scan[kEmitWaves];
+	__shared__ uint32_t s_long[kEmitLong];      // items whose segments are walked
+	__shared__ uint32_t s_nlong, s_carry;
+	const uint32_t zi = blockIdx.x + a.z0;
+	const uint32_t tid = threadIdx.x;
+	if (a.slice_err[zi]) {      // uniform; the run ends with this error (check_walk_errors)
+		if (tid == 0) { a.n_raw[zi] = 0; a.n_valid[zi] = 0; f.payload_len[zi] = 0; f.boc_len[zi] = 0; }
+		return;
+	}
+	const uint32_t n = a.n_items[zi];
+	const uint32_t nch = a.n_chains[zi];
+	const uint64_t nb = a.nbase[zi], kb = a.kbase[zi];
+	const uint32_t* items = a.items + a.ibase[zi];
+	uint32_t* off = a.item_off + a.ibase[zi];
+	const uint32_t* dlen = a.dart_len + nb * 4u;
+	const uint8_t* dinl = a.dart_inline + nb * 4u;
+	if (tid == 0) s_nlong = 0u;
+	__syncthreads();
+
+	// ---- offsets (k_trail_offsets): code offset of every item in raw chain order; the segments to walk are listed on the way
+	uint32_t total = 0;
+	{
+		constexpr uint32_t kPer = 4;
+		for (uint32_t i0 = 0; i0 < n; i0 += kEmitBlock * kPer) {
+			uint32_t len[kPer], cnt = 0;
+#pragma unroll
+			for (uint32_t q = 0; q < kPer; q++) {
+				const uint32_t i = i0 + tid * kPer + q;
+				len[q] = 0;
+				if (i < n) {
+					const uint32_t it = items[i];
+					const uint32_t kind = it & kItemMask;
+					if (kind == kItemSeg) {
+						const uint32_t d = it & ~kItemMask;
+						len[q] = dlen[d];
+						if (len[q] > kInlineCodes || (len[q] && !dinl[d])) {
+							const uint32_t j = atomicAdd(&s_nlong, 1u);
+							if (j < kEmitLong) s_long[j] = i;
+						}
+					}
+					else if (kind == kItemCtl) len[q] = 2u;
+				}
+				cnt += len[q];
+			}
+			uint32_t v[1] = { cnt }, tot[1];
+			block_excl_add<1, kEmitWaves>(v, tot, s_scan);
+			uint32_t o = total + v[0];
+#pragma unroll
+			for (uint32_t q = 0; q < kPer; q++) {
+				const uint32_t i = i0 + tid * kPer + q;
+				if (i < n) off[i] = o;
+				o += len[q];
+			}
+			total += tot[0];
+		}
+	}
+	__syncthreads();
+	__threadfence_block();
+	if (total > a.ccap[zi]) {      // uniform
+		if (tid == 0) { atomicOr(a.slice_err + zi, TRAIL_ERR_CAPACITY); a.n_raw[zi] = total; a.n_valid[zi] = total; f.payload_len[zi] = 0; f.boc_len[zi] = 0; }
+		return;
+	}
+
+	// ---- chain tables: start vertex, first item, first raw code offset
+	const EmitSlice sl = { zi, n, nch, total, wcap, items, off, dlen, nb };
+	uint32_t* words = s_emit + 2u * tcap;
+	const uint32_t* g_node = a.chain_node + kb;
+	const uint32_t* g_item0 = a.chain_item0 + kb;
+	if (nch <= tcap) {      // uniform
+		uint32_t* s_item0 = s_emit;
+		uint32_t* s_dst = s_emit + tcap;
+		uint32_t* s_node = words;
+		uint32_t* s_order = words + tcap;
+		uint32_t* s_vstart = words + 2u * tcap;
+		for (uint32_t c = tid; c < nch; c += kEmitBlock) {
+			const uint32_t i0 = g_item0[c];
+			s_item0[c] = i0; s_node[c] = g_node[c]; s_vstart[c] = i0 < n ? off[i0] : total;
+		}
+		__syncthreads();
+		emit_chains_and_codes(a, f, sl, words, s_node, s_item0, s_vstart, s_order, s_dst, s_long, &s_nlong, &s_carry);
+	}
+	else {
+		uint32_t* g_vstart = a.chain_off + kb;
+		for (uint32_t c = tid; c < nch; c += kEmitBlock) { const uint32_t i0 = g_item0[c]; g_vstart[c] = i0 < n ? off[i0] : total; }
+		__syncthreads();
+		__threadfence_block();
+		emit_chains_and_codes(a, f, sl, words, g_node, g_item0, g_vstart, f.chain_order + kb, f.chain_dst + kb, s_long, &s_nlong, &s_carry);
 	}
 }
 
@@ -1421,6 +1705,40 @@ struct CrackResult {
 // Dynamic LDS of k_trail_walk for slices of up to `max_special` nodes (+ what k_trail_loops / _components add)
 inline size_t trail_walk_lds(uint32_t max_special) { return (static_cast<size_t>(max_special) + 256) * 16 + 1024; }
 
+// Whether k_trail_emit takes the place of k_trail_offsets + k_trail_expand + k_finish for a volume, and with how much LDS.
+// Decided before the launch from what the host has: the crack edges of the largest slice and the largest chain
+// capacity.  A slice's code points are its crack edges plus two per 'b' and 't'; the word buffer is sized for an eighth
+// more than the edges (a slice with more is emitted in windows: correct, slower).  Static and dynamic LDS together stay
+// within kEmitLdsCap, so that two workgroups share a CU; a volume whose largest slice asks for more takes the three kernels.
+// CKL_TRAIL_EMIT=0 forces the three kernels; CKL_TRAIL_EMIT_LDS=n (testing) puts n bytes in kEmitLdsCap's place;
+// CKL_TRAIL_EMIT_WORDS=n (testing) shrinks the word buffer to n words, so that small slices are emitted in windows too.
+constexpr size_t kEmitLdsCap = 80 * 1024;
+struct EmitPlan {
+	bool fused = false;
+	uint32_t tcap = 0, wcap = 0;      // chains staged in LDS, words of code points
+	size_t dyn = 0, need = 0;         // dynamic LDS in bytes; static + dynamic
+};
+EmitPlan emit_plan(uint64_t max_edges, uint32_t max_kcap, int max_lds) {
+	EmitPlan p;
+	static const size_t static_lds = [] {      // the kernel's own arrays: asked once (the same code object on every device)
+		hipFuncAttributes fattr;
+		CKL_HIP(hipFuncGetAttributes(&fattr, reinterpret_cast<const void*>(&k_trail_emit)));
+		return static_cast<size_t>(fattr.sharedSizeBytes);
+	}();
+	p.tcap = std::min<uint32_t>(kFinishChains, ((max_kcap + 15u) / 16u) * 16u);
+	const uint64_t words = (max_edges + max_edges / 8 + 1024 + 15) / 16;
+	p.wcap = static_cast<uint32_t>(std::min<uint64_t>(words, 1u << 28));
+	if (const char* env = getenv("CKL_TRAIL_EMIT_WORDS")) p.wcap = static_cast<uint32_t>(std::max(1, std::min<int>(atoi(env), static_cast<int>(p.wcap))));      // testing: windows
+	p.dyn = 4 * (2 * static_cast<size_t>(p.tcap) + std::max<size_t>(3 * static_cast<size_t>(p.tcap), p.wcap));
+	p.need = static_lds + p.dyn;
+	size_t cap = kEmitLdsCap;
+	if (const char* env = getenv("CKL_TRAIL_EMIT_LDS")) cap = static_cast<size_t>(std::max(0, atoi(env)));
+	cap = std::min(cap, static_cast<size_t>(std::max(0, max_lds)));
+	const char* sw = getenv("CKL_TRAIL_EMIT");
+	p.fused = !(sw && !strcmp(sw, "0")) && words < (1u << 28) && p.need <= cap;
+	return p;
+}
+
 // k_finish's view of the session (the arrays are there: crack_pass has sized them)
 FinishArgs finish_args(const ckl_encoder& e, int64_t sx, int64_t sy, int markov_order) {
 	FinishArgs fa;
@@ -1522,7 +1840,8 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 	std::vector<uint64_t> nbase(ns), cobase(ns), ibase(ns);
 	std::vector<uint32_t> ncap(ns), cocap(ns), icap(ns);
 	uint64_t ctot = 0, stot = 0, ktot = 0, ntot = 0, cotot = 0, itot = 0;
-	uint32_t max_ncap = 0, max_cocap = 0, max_icap = 0, max_special = 0;
+	uint32_t max_ncap = 0, max_cocap = 0, max_icap = 0, max_special = 0, max_kcap = 0;
+	uint64_t max_edges = 0;
 	bool any = false;
 	for (uint32_t zi = 0; zi < ns; zi++) {
 		const uint64_t E = crack_edges(e, sx, sy, zi, rq.permissible);
@@ -1545,6 +1864,8 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 		max_cocap = std::max<uint32_t>(max_cocap, cocap[zi]);
 		max_icap = std::max<uint32_t>(max_icap, icap[zi]);
 		max_special = std::max<uint32_t>(max_special, e.count_special[zi]);
+		max_kcap = std::max<uint32_t>(max_kcap, kcap[zi]);
+		max_edges = std::max<uint64_t>(max_edges, E);
 	}
 	result.any_chain = any;
 	if (g_ht && g_ht->on) {
@@ -1560,11 +1881,20 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 	tables.add(e.d_cbase, cbase); tables.add(e.d_ccap, ccap);
 	tables.add(e.d_sbase, sbase); tables.add(e.d_scap, scap);
 	tables.add(e.d_kbase, kbase); tables.add(e.d_kcap, kcap);
-	e.d_cp.ensure(ctot); e.d_fcode.ensure(ctot);
+	// one volume takes one path behind k_trail_items: k_trail_emit, or k_trail_offsets + k_trail_expand + k_finish with a
+	// byte per code point in d_cp and d_fcode
+	int max_lds = 0;
+	CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
+	EmitPlan emit;
+	if (!reuse_trail) {
+		emit = emit_plan(max_edges, max_kcap, max_lds);
+		e.emit_fused = emit.fused; e.emit_lds = emit.need;
+		if (!emit.fused) { e.d_cp.ensure(ctot); e.d_fcode.ensure(ctot); e.d_chain_clen.ensure(ktot); e.d_chain_vstart.ensure(ktot); }
+	}
 	if (markov_order) e.d_dcode.ensure(ctot);
 	e.d_stack_node.ensure(stot); e.d_stack_code.ensure(stot);
-	e.d_chain_node.ensure(ktot); e.d_chain_off.ensure(ktot); e.d_chain_clen.ensure(ktot);
-	e.d_chain_order.ensure(ktot); e.d_chain_dst.ensure(ktot); e.d_chain_vstart.ensure(ktot);
+	e.d_chain_node.ensure(ktot); e.d_chain_off.ensure(ktot);
+	e.d_chain_order.ensure(ktot); e.d_chain_dst.ensure(ktot);
 	e.d_n_chains.ensure(ns); e.d_n_raw.ensure(ns); e.d_n_valid.ensure(ns);
 	e.d_payload_len.ensure(ns); e.d_boc_len.ensure(ns);
 	const int xw = byte_width(static_cast<uint64_t>(sx) + 1), yw = byte_width(static_cast<uint64_t>(sy) + 1);
@@ -1610,8 +1940,6 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 		TrailArgs ta = trail_args(e, sx, sy, ns);
 		const FinishArgs fa = finish_args(e, sx, sy, markov_order);
 		if (kTuning && getenv("CKL_TRAIL_DIAG")) { d_tdbg.ensure(16); CKL_HIP(hipMemsetAsync(d_tdbg.p, 0, 128, s)); ta.dbg = d_tdbg.p; }
-		int max_lds = 0;
-		CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
 		const size_t budget = static_cast<size_t>(max_lds > 1024 ? max_lds - 1024 : 0);
 		const uint32_t dart_blocks = (4 * max_ncap + kWalkChunk * kWaves - 1) / (kWalkChunk * kWaves);
 		// union-find table (4 bytes per node) and component minima (8) of k_trail_components in LDS
@@ -1641,9 +1969,15 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 		hipLaunchKernelGGL(k_trail_walk, dim3(ns), dim3(kWave), lds, s, ta, static_cast<uint32_t>(lds));
 		CKL_HIP(hipEventRecord(e.evd1, s));
 		hipLaunchKernelGGL(k_trail_items, dim3(ns), dim3(kItemsBlock), 0, s, ta);
-		hipLaunchKernelGGL(k_trail_offsets, dim3(ns), dim3(kBlock), 0, s, ta);
-		hipLaunchKernelGGL(k_trail_expand, dim3((max_icap + kExpandChunk * kWaves - 1) / (kExpandChunk * kWaves), ns), dim3(kBlock), 0, s, ta);
-		hipLaunchKernelGGL(k_finish, dim3(ns), dim3(kFinishBlock), 0, s, fa);
+		if (emit.fused) {
+			CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trail_emit), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(emit.dyn)));
+			hipLaunchKernelGGL(k_trail_emit, dim3(ns), dim3(kEmitBlock), emit.dyn, s, ta, fa, emit.tcap, emit.wcap);
+		}
+		else {
+			hipLaunchKernelGGL(k_trail_offsets, dim3(ns), dim3(kBlock), 0, s, ta);
+			hipLaunchKernelGGL(k_trail_expand, dim3((max_icap + kExpandChunk * kWaves - 1) / (kExpandChunk * kWaves), ns), dim3(kBlock), 0, s, ta);
+			hipLaunchKernelGGL(k_finish, dim3(ns), dim3(kFinishBlock), 0, s, fa);
+		}
 	}
 	HT_MARK("c:enqueue");
 	if (kTuning && getenv("CKL_TRAIL_DIAG")) trail_diag(e, ns, d_tdbg.p, max_special, trail_lds_used);
@@ -2715,6 +3049,13 @@ int ckl_encoder_walk_paths(ckl_encoder* e, uint32_t* fast_slices, uint32_t* comp
 		if (fast_slices) *fast_slices = fast;
 		if (compiled_slices) *compiled_slices = plain;
 	});
+}
+
+int ckl_encoder_emit_path(const ckl_encoder* e, int* fused, uint64_t* lds_bytes) {
+	if (!e) { set_last_error("crackle_amd: null encoder"); return CKL_ERR_ARG; }
+	if (fused) *fused = e->emit_fused ? 1 : 0;
+	if (lds_bytes) *lds_bytes = e->emit_lds;
+	return CKL_OK;
 }
 
 int ckl_encoder_walk_step_kinds(ckl_encoder* e, uint32_t* counts, uint32_t max_slices, uint32_t* n_slices) {

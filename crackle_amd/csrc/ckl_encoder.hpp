@@ -106,6 +106,8 @@ struct ckl_encoder {
 	bool trail_zeroed = false;         // trail_prezero() ran on the stream since the last trail: crack_pass skips its fills
 	DevBuf<uint64_t> t_nbase, t_cobase, t_ibase;
 	DevBuf<uint32_t> t_ncap, t_cocap, t_icap, t_max_steps;
+	bool emit_fused = false;                     // the last crack pass that built a trail emitted it with k_trail_emit (emit_plan, ckl_encode.hip)
+	size_t emit_lds = 0;                         // ... the LDS its plan asked for, static + dynamic
 	size_t last_trail_slices = 0;                // slices of the last crack pass (the layout of t_counters)
 	DevBuf<uint32_t> t_counters;                 // n_nodes | n_snap | n_corners | n_starts | n_items | n_events | seg_len_sum, [nslices] each
 	DevBuf<uint32_t> t_node_vertex, t_vert2node, t_corner_vertex;

@@ -530,6 +530,14 @@ class HipBackend:
       raise RuntimeError(_lib.last_error())
     return f.value, c.value
 
+  def emit_path(self) -> Tuple[bool, int]:
+    """(k_trail_emit packed the last encode's crack codes, the LDS in bytes its plan asked for); False: the volume
+    took k_trail_offsets + k_trail_expand + k_finish."""
+    f, n = C.c_int(), C.c_uint64()
+    if self._enc and self._L.ckl_encoder_emit_path(self._enc, C.byref(f), C.byref(n)) != _lib.CKL_OK:
+      raise RuntimeError(_lib.last_error())
+    return bool(f.value), int(n.value)
+
   def walk_step_kinds(self, max_slices: int = 1 << 16):
     """(slices, 5) array of the last encode's serial trail by kind of step: along the only remaining edge, branch +
     lowest edge, dead end, chain end, longest run without a branch (ckl_encoder_walk_step_kinds)."""

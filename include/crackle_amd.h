@@ -433,6 +433,11 @@ int ckl_encoder_last_timing(const ckl_encoder* e, float* pipeline_ms, float* dom
  * 16-bit fields, or a branch stack beyond its LDS part).  Tests assert the path with it; no reference
  * counterpart. */
 int ckl_encoder_walk_paths(ckl_encoder* e, uint32_t* fast_slices, uint32_t* compiled_slices);
+/* Which kernels packed the last run's crack codes behind the trail's items: *fused = 1 for k_trail_emit (one workgroup
+ * per slice, the code points packed in LDS), 0 for k_trail_offsets + k_trail_expand + k_finish (a volume whose largest
+ * slice asks for more LDS than two workgroups per CU leave, or CKL_TRAIL_EMIT=0).  *lds_bytes: what k_trail_emit
+ * asked for, static + dynamic, on either path.  Tests assert the path with it; no reference counterpart. */
+int ckl_encoder_emit_path(const ckl_encoder* e, int* fused, uint64_t* lds_bytes);
 /* Diagnostic: the serial crack trail of the last ckl_encoder_run, by kind of step.  counts[5 * z + k] for slice z:
  * k = 0 steps along the only remaining edge of a node, 1 steps that push a branch and pick the lowest edge
  * (create_crack_codes' one real decision, src/crackcodes.hpp:399-433), 2 dead ends (returns to the branch

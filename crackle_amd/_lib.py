@@ -6,6 +6,7 @@ device is usable.
 """
 import ctypes as C
 import os
+import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CKL_TUNING_LIB=1 (kernel work only): the -DCKL_TUNING build with cycle stamps
@@ -141,25 +142,31 @@ EXPORTS = {
 }
 
 _lib = None
+_lib_lock = threading.Lock()
 
 
 def lib():
-  """Loads libcrackle_amd.so, failing loudly when it has not been built."""
+  """Loads libcrackle_amd.so, failing loudly when it has not been built.  Any thread may arrive first:
+  the library is loaded and declared under a lock, and published only once every export has its types."""
   global _lib
-  if _lib is None:
-    if not os.path.exists(LIB_PATH):
-      raise ImportError(
-        f"{LIB_PATH} is missing: build the HIP extension first "
-        "(python -m crackle_amd.build, or __graft_entry__.build()). "
-        "crackle_amd has no CPU fallback."
-      )
-    L = C.CDLL(LIB_PATH)
-    for name, (res, args) in EXPORTS.items():
-      f = getattr(L, name)   # AttributeError here = ABI drift: fail loudly
-      f.restype = res
-      f.argtypes = args
-    _lib = L
-  return _lib
+  L = _lib
+  if L is not None:
+    return L
+  with _lib_lock:
+    if _lib is None:
+      if not os.path.exists(LIB_PATH):
+        raise ImportError(
+          f"{LIB_PATH} is missing: build the HIP extension first "
+          "(python -m crackle_amd.build, or __graft_entry__.build()). "
+          "crackle_amd has no CPU fallback."
+        )
+      L = C.CDLL(LIB_PATH)
+      for name, (res, args) in EXPORTS.items():
+        f = getattr(L, name)   # AttributeError here = ABI drift: fail loudly
+        f.restype = res
+        f.argtypes = args
+      _lib = L
+    return _lib
 
 
 def last_error() -> str:

@@ -3,6 +3,7 @@
 #include "ckl_common.hpp"
 
 #include <algorithm>
+#include <exception>
 #include <mutex>
 
 namespace ckl {
@@ -23,6 +24,20 @@ int select_device(int device) {
 	}
 	CKL_HIP(hipSetDevice(device));
 	return count;
+}
+
+void allow_dynamic_lds(const void* fn, int device, size_t bytes) {
+	if (bytes <= 48u * 1024u) return;      // within every kernel's default limit
+	struct Limit { const void* fn; int device; size_t bytes; };
+	static std::mutex mu;
+	static std::vector<Limit>& limits = *new std::vector<Limit>();      // never destroyed: threads may still be in calls at exit
+	std::lock_guard<std::mutex> lock(mu);
+	Limit* at = nullptr;
+	for (Limit& l : limits) if (l.fn == fn && l.device == device) { at = &l; break; }
+	if (at && at->bytes >= bytes) return;
+	CKL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+	if (at) at->bytes = bytes;
+	else limits.push_back({ fn, device, bytes });
 }
 
 void wait_for_default_stream(hipStream_t s, hipEvent_t ev) {
@@ -83,8 +98,16 @@ void* pool_alloc(size_t bytes, int* device) {
 	return pool_poison(p, bytes);
 }
 
+// A block released while an exception unwinds its owner's frame (a DevBuf or HostOut local to a call that failed
+// half-way) may still be written by work that call has queued, and the pools hand it to any thread's next session:
+// wait for the device first.  Only error paths pay for this.
+static void settle_if_unwinding() {
+	if (std::uncaught_exceptions() > 0) (void)hipDeviceSynchronize();
+}
+
 void pool_free(void* p, size_t bytes, int device) {
 	if (!p) return;
+	settle_if_unwinding();
 	int dev = device;
 	if (dev < 0) (void)hipGetDevice(&dev);
 	{
@@ -160,6 +183,7 @@ bool host_out_is_pinned(const void* p) {
 
 void host_out_free(void* p) {
 	if (!p) return;
+	settle_if_unwinding();
 	HostBlock b = { nullptr, 0 };
 	bool drop = false;
 	{

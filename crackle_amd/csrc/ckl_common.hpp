@@ -182,6 +182,11 @@ inline void with_label_type(int width, F&& f) {
 
 void set_last_error(const std::string& msg);
 int select_device(int device);   // throws CKL_ERR_NO_DEVICE
+// A kernel's dynamic LDS beyond the default limit has to be allowed per device and function, and the limit is a
+// property of the process, not of a call: this is the only place that sets it.  It only ever grows (a thread that
+// needs 8 KiB never takes away the 100 KiB another thread is about to launch with), and the lock is held across
+// the runtime call, so whoever returns from here may launch with `bytes`.  `device` is the current device.
+void allow_dynamic_lds(const void* fn, int device, size_t bytes);
 
 // The body of a C entry point: what it throws becomes the last error and a status.  A body returns
 // nothing (CKL_OK) or a status, e.g. the one another entry point gave it, whose last-error text then

@@ -44,7 +44,6 @@
 #include <memory>
 #include <mutex>
 #include <type_traits>
-#include <tuple>
 
 namespace ckl {
 
@@ -2125,17 +2124,6 @@ std::shared_ptr<DevBuf<uint32_t>> geom_table(int device, uint64_t sxy, hipStream
 // buf: the stream on the host — all of it, or (stream_device given: the stream is resident in HBM already
 // and stays the caller's) an image that holds header, z-index, label section head, markov model and crc
 // tail at their offsets and nothing of the crack codes.
-// a kernel's dynamic LDS beyond the default 64 KiB has to be allowed once per device and function
-void allow_dynamic_lds(const void* fn, int device, size_t bytes) {
-	if (bytes <= 48u * 1024u) return;
-	static std::mutex mu;
-	static std::vector<std::tuple<const void*, int, size_t>>& done = *new std::vector<std::tuple<const void*, int, size_t>>();
-	std::lock_guard<std::mutex> lock(mu);
-	for (auto& e : done) if (std::get<0>(e) == fn && std::get<1>(e) == device && std::get<2>(e) >= bytes) return;
-	CKL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
-	done.emplace_back(fn, device, bytes);
-}
-
 void decoder_build(ckl_decoder& d, const uint8_t* buf, uint64_t n, int64_t z_start, int64_t z_end, const uint8_t* stream_device = nullptr) {
 	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
 	d.head = Header::parse(buf, n);
@@ -3157,16 +3145,7 @@ static std::unique_ptr<ckl_decoder> decoder_new(int device) {
 		CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
 	}
 	d->max_lds = max_lds;
-	// the kernels' dynamic LDS limits are set once per device and size
-	static std::mutex mu;
-	static std::vector<std::pair<int, size_t>>& done = *new std::vector<std::pair<int, size_t>>();
-	auto once = [&](int key, size_t bytes) {
-		std::lock_guard<std::mutex> lock(mu);
-		const std::pair<int, size_t> k(device * 8 + key, bytes);
-		if (std::find(done.begin(), done.end(), k) != done.end()) return false;
-		done.push_back(k);
-		return true;
-	};
+	// the kernels' dynamic LDS limits: allow_dynamic_lds, as everywhere
 	{
 		// LDS control tables of k_decode_cracks: as many symbols as the workgroup's LDS allows
 		const size_t budget = static_cast<size_t>(max_lds > 4096 ? max_lds - 4096 : 0);   // static LDS of the kernel: ~2.4 KiB
@@ -3179,11 +3158,8 @@ static std::unique_ptr<ckl_decoder> decoder_new(int device) {
 		// one workgroup per CU either way: the raster phase takes whatever LDS is left for
 		// its bands (1024x1024 slices: 2 passes instead of 3)
 		d->lds_bytes = getenv("CKL_LDS_CONTROLS") ? crack_lds_bytes(nctl) : std::max(crack_lds_bytes(nctl), budget & ~static_cast<size_t>(15));
-		const int bytes = static_cast<int>(d->lds_bytes);
-		if (once(0, d->lds_bytes)) {
-			CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_cracks<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-			if constexpr (kTuning) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_cracks<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-		}
+		allow_dynamic_lds(reinterpret_cast<const void*>(&k_decode_cracks<false>), device, d->lds_bytes);
+		if constexpr (kTuning) allow_dynamic_lds(reinterpret_cast<const void*>(&k_decode_cracks<true>), device, d->lds_bytes);
 	}
 	{
 		// k_crack_match: two workgroups per CU, each with half of the CU's LDS for its control tables
@@ -3196,7 +3172,7 @@ static std::unique_ptr<ckl_decoder> decoder_new(int device) {
 		d->rec_lds = (rec_lds_bytes(nctl) + 15) & ~static_cast<size_t>(15);
 		// markov streams are expanded in the same LDS: give them all of the half
 		if (!getenv("CKL_LDS_CONTROLS")) d->rec_lds = std::max(d->rec_lds, budget & ~static_cast<size_t>(15));
-		if (nctl && once(1, d->rec_lds)) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crack_match<kRecBlock>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(d->rec_lds)));
+		if (nctl) allow_dynamic_lds(reinterpret_cast<const void*>(&k_crack_match<kRecBlock>), device, d->rec_lds);
 	}
 	return d;
 }
@@ -3394,9 +3370,11 @@ int ckl_decoder_set_stage_events(ckl_decoder* d, int on) {
 
 void ckl_decoder_destroy(ckl_decoder* d) {
 	if (!d) return;
-	// a session that was built and never run still has its descriptor upload in flight: the staging block and the
-	// stream must not go back to their caches under it
-	if (d->pending_upload && d->stream) (void)hipStreamSynchronize(d->stream);
+	// a session that was built and never run still has its descriptor upload in flight, one whose run ended in an
+	// error whatever that run had queued: the blocks and the stream must not go back to their caches, which other
+	// threads' sessions draw from, under it.  (After a run that succeeded the stream is idle and this returns at once.)
+	if (d->stream) (void)hipStreamSynchronize(d->stream);
+	for (hipStream_t cs : d->chunk_stream) if (cs) (void)hipStreamSynchronize(cs);
 	// stream and events go to the cache (at most four sets are kept), idle: every run waits for its own work
 	if (d->stream) {
 		std::lock_guard<std::mutex> lock(g_session_mutex);

@@ -1946,13 +1946,13 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 		size_t clds = (static_cast<size_t>(max_special) + 1024) * 12;
 		if (const char* env = getenv("CKL_TRAIL_LDS")) clds = static_cast<size_t>(std::max(0, atoi(env)));
 		clds = (std::min(budget, std::max<size_t>(clds, 1024)) / 16) * 16;
-		CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trail_components), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(clds)));
+		allow_dynamic_lds(reinterpret_cast<const void*>(&k_trail_components), e.device, clds);
 		// node tables of k_trail_walk in LDS + 16 KiB of branch stack when that fits
 		size_t lds = trail_walk_lds(max_special);      // k_trail_walk: 12 bytes of record + 4 of branch stack per node
 		if (const char* env = getenv("CKL_TRAIL_LDS")) lds = static_cast<size_t>(std::max(0, atoi(env)));   // testing: small values force the global tables
 		lds = std::min(budget, std::max<size_t>(lds, 4096));
 		lds = (lds / 16) * 16;
-		CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trail_walk), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+		allow_dynamic_lds(reinterpret_cast<const void*>(&k_trail_walk), e.device, lds);
 		trail_lds_used = lds;
 		HT_MARK("c:setup");
 
@@ -1970,7 +1970,7 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 		CKL_HIP(hipEventRecord(e.evd1, s));
 		hipLaunchKernelGGL(k_trail_items, dim3(ns), dim3(kItemsBlock), 0, s, ta);
 		if (emit.fused) {
-			CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trail_emit), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(emit.dyn)));
+			allow_dynamic_lds(reinterpret_cast<const void*>(&k_trail_emit), e.device, emit.dyn);
 			hipLaunchKernelGGL(k_trail_emit, dim3(ns), dim3(kEmitBlock), emit.dyn, s, ta, fa, emit.tcap, emit.wcap);
 		}
 		else {
@@ -2005,7 +2005,7 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 			e.d_hist.ensure(rows * 4);
 			CKL_HIP(hipMemsetAsync(e.d_hist.p, 0, rows * 4 * sizeof(uint32_t), s));
 			const uint32_t hist_lds = (rows * 4 <= 16384) ? static_cast<uint32_t>(rows * 4) : 0u;    // order <= 6: 64 KiB
-			if (hist_lds * 4 > 48 * 1024) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_markov_hist), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(hist_lds * 4)));
+			allow_dynamic_lds(reinterpret_cast<const void*>(&k_markov_hist), e.device, hist_lds * 4);
 			hipLaunchKernelGGL(k_markov_hist, dim3(ns), dim3(kBlock), hist_lds * sizeof(uint32_t), s, e.d_dcode.p, e.d_cbase.p, e.d_n_valid.p, markov_order, e.d_hist.p, hist_lds);
 			result.hist = download(e.d_hist.p, rows * 4, s);
 			if (rq.goal == CrackGoal::HISTOGRAM) { check_walk_errors(e, ns); return result; }
@@ -2193,13 +2193,13 @@ void flat_launch_resolve(ckl_encoder& e, const void* labels, int64_t sx, int64_t
 	const size_t tab_bytes = static_cast<size_t>(cap) * sizeof(uint32_t);
 	if (e.label_src) {
 		// no volume: the slots receive the components' first pixels, flat_collect turns them into labels
-		if (tab_bytes > 48u * 1024u) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slice_resolve_enc_pixels), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tab_bytes)));
+		allow_dynamic_lds(reinterpret_cast<const void*>(&k_slice_resolve_enc_pixels), e.device, tab_bytes);
 		hipLaunchKernelGGL(k_slice_resolve_enc_pixels, dim3(ns), dim3(kResolveBlock), tab_bytes, s, g, sa, ra, en, e.d_ncomp.p);
 		return;
 	}
 	with_label_type(e.dtype_bytes, [&](auto t) {
 		typedef typename decltype(t)::type LABEL;
-		if (tab_bytes > 48u * 1024u) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slice_resolve_enc<LABEL>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tab_bytes)));
+		allow_dynamic_lds(reinterpret_cast<const void*>(&k_slice_resolve_enc<LABEL>), e.device, tab_bytes);
 		hipLaunchKernelGGL(k_slice_resolve_enc<LABEL>, dim3(ns), dim3(kResolveBlock), tab_bytes, s, g, sa, ra, en, e.d_ncomp.p);
 	});
 }
@@ -3096,11 +3096,11 @@ int ckl_compress(
 	catch (const Error& err) { set_last_error(err.what()); return err.status; }
 	const int rc = ckl_encoder_create(sx, sy, sz, dtype_bytes, device, &e);
 	if (rc != CKL_OK) return rc;
+	DevBuf<uint8_t> tmp;      // (in front of the session: ~ckl_encoder waits for its streams before the labels go back to the pool, also when the run failed)
 	const EncoderPtr owner(e);
 	return guard([&]() -> int {
 		const uint64_t bytes = static_cast<uint64_t>(sx) * sy * sz * dtype_bytes;
 		const void* dev_labels = labels;
-		DevBuf<uint8_t> tmp;
 		if (labels_mem == CKL_MEM_HOST && bytes) {
 			if (!labels) throw Error(CKL_ERR_ARG, "crackle_amd: null labels");
 			tmp.ensure(bytes);

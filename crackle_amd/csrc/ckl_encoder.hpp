@@ -125,8 +125,10 @@ struct ckl_encoder {
 		if (evd1) (void)hipEventDestroy(evd1);
 		if (ev_in) (void)hipEventDestroy(ev_in);
 		if (ev_prezero) (void)hipEventDestroy(ev_prezero);
-		if (stream) (void)hipStreamDestroy(stream);
-		if (stream2) (void)hipStreamDestroy(stream2);
+		// the buffers below go back to a pool that other threads' sessions draw from: nothing of this session may
+		// still be queued then (a run that ended in an error leaves its streams as they were)
+		if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+		if (stream2) { (void)hipStreamSynchronize(stream2); (void)hipStreamDestroy(stream2); }
 		if (stream_copy) { (void)hipStreamSynchronize(stream_copy); (void)hipStreamDestroy(stream_copy); }
 		if (stream_tab) { (void)hipStreamSynchronize(stream_tab); (void)hipStreamDestroy(stream_tab); }
 		if (ev_codes) (void)hipEventDestroy(ev_codes);

@@ -742,7 +742,7 @@ void decoder_label_stats(ckl_decoder& d, uint64_t capacity, uint64_t* labels, ui
 		uint32_t fit = static_cast<uint32_t>(std::max(0, d.max_lds - 1024)) / kStatsBytesPerComp;
 		if (const char* env = getenv("CKL_STATS_LDS_COMPS")) fit = std::min<uint32_t>(fit, static_cast<uint32_t>(std::max(0, atoi(env))));   // testing: forces the run-by-run merge
 		sa.lds_comps = std::min<uint32_t>((d.max_comp + 1) & ~1u, fit & ~1u);
-		CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_run_stats), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sa.lds_comps * kStatsBytesPerComp)));
+		allow_dynamic_lds(reinterpret_cast<const void*>(&k_run_stats), d.device, static_cast<size_t>(sa.lds_comps * kStatsBytesPerComp));
 	}
 	RunRequest rq = { Goal::STATS };
 	rq.stats = &sa;
@@ -1253,7 +1253,7 @@ void decoder_point_cloud(ckl_decoder& d, const uint64_t* sel, uint64_t n_sel, bo
 	const uint32_t vis_words = (sxy + 31) / 32;
 	const uint32_t cand_words = ((vis_words + 1) & ~1u) + 2 * kContourWindow;      // a scan window may start at the last word
 	const bool lds_vis = !getenv("CKL_CONTOUR_HBM_VISITED") && static_cast<uint64_t>(vis_words) * 4 + 256 <= static_cast<uint64_t>(std::max(0, d.max_lds));
-	if (lds_vis) CKL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_contours<true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(vis_words * 4)));
+	if (lds_vis) allow_dynamic_lds(reinterpret_cast<const void*>(&k_trace_contours<true>), d.device, static_cast<size_t>(vis_words * 4));
 
 	// contours of all slices: per slice the kept ones in discovery order
 	struct Kept { uint32_t zi, offset, len, rot, first, comp; };

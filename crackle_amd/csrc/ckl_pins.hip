@@ -343,6 +343,8 @@ void host_parallel_for(size_t n, size_t grain, const std::function<void(size_t, 
 		catch (...) { errors[t] = "error"; }
 	};
 	if (!HostPool::get().run(want, job)) {
+		static const bool trace = getenv("CKL_POOL_TRACE") != nullptr;      // diagnostic (and the threads test's evidence that this branch ran)
+		if (trace) fprintf(stderr, "[ckl pool] host pool taken: %zu threads of the caller's own\n", want);
 		std::vector<std::thread> pool;
 		for (size_t t = 0; t < want; t++) pool.emplace_back([&, t]() { job(t); });
 		for (auto& th : pool) th.join();

@@ -16,6 +16,14 @@
  * order", src/crackle.hpp:219).  All compute runs on the selected HIP device;
  * there is no CPU fallback — without a usable device the calls fail with
  * CKL_ERR_NO_DEVICE.
+ *
+ * Threads: any number of host threads may be inside the one-shot calls (every
+ * function that takes a stream or a volume and a device) at the same time, on the
+ * same or on different devices.  A session object (ckl_decoder, ckl_encoder)
+ * belongs to one thread at a time: threads may each hold their own, no two may be
+ * inside calls on the same session together; a session may be handed from one
+ * thread to another between calls.  ckl_last_error() is the calling thread's
+ * own.  ckl_free may be called from any thread.  
  */
 #ifndef CRACKLE_AMD_H
 #define CRACKLE_AMD_H

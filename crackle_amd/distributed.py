@@ -3,7 +3,8 @@ RCCL/xGMI (backend "nccl") on a node, or gloo in CPU tests of the orchestration.
 
 Slices of one volume are independent on this path (reference: one thread-pool task
 per z-slice, src/crackcodes.hpp:510-518, src/labels.hpp:56-88, src/crackle.hpp:584-660),
-so rank r owns slices [r*sz, (r+1)*sz).  What is *not* per-slice in the reference are
+so the ranks own consecutive z-slabs in rank order, of any depths, zero included (a rank without
+slices joins every collective with an empty contribution).  What is *not* per-slice in the reference are
 three whole-volume decisions, each an all-reduce / all-gather of a few
 bytes — latency-bound, nothing bulky ever crosses xGMI except the compressed slabs
 (~1 % of the input) gathered to the rank that writes the file:
@@ -129,6 +130,22 @@ class _SlabSections:
     c0 = off + nlb + mb
     self.cracks = a[c0:c0 + crack_bytes]
     self.crcs = a[len(a) - 4 * sz:]
+
+  @classmethod
+  def empty(cls, sx: int, sy: int, stored_width: int, uniq: np.ndarray):
+    """What a rank without slices contributes: no z-index entry, component count, key, crack code or crc; `uniq` is
+    the merged unique list where the ranks exchanged it in front of their sections (int64 bit patterns), else empty."""
+    self = cls.__new__(cls)
+    none = np.zeros(0, np.uint8)
+    self.header = None      # header and model are written by a rank that holds slices
+    self.sz = 0
+    self.stored_width = int(stored_width)
+    self.comp_width = _byte_width(sx * sy)
+    self.uniq = np.ascontiguousarray(uniq).view(np.int64)
+    self.key_width = _byte_width(len(self.uniq))
+    self.n_keys = 0
+    self.zidx = self.comp = self.keys_raw = self.model = self.cracks = self.crcs = none
+    return self
 
 
 class SharedStream:
@@ -306,6 +323,21 @@ class HipDecodeSession:
       self.close()
     except Exception:
       pass
+
+
+class _NoSlicesSession:
+  """The decode session of a rank without slices: run() takes an output of no elements and writes nothing."""
+
+  def run(self, out, label: Optional[int] = None):
+    n = out.numel() if hasattr(out, "numel") else out.size
+    if n:
+      raise RuntimeError("crackle_amd: this rank decodes no slice; its output must be empty")
+
+  def timing(self) -> Tuple[float, float]:
+    return 0.0, 0.0
+
+  def close(self):
+    pass
 
 
 class HipBackend:
@@ -591,8 +623,9 @@ class ShardedCodec:
     return torch.stack(parts).cpu().numpy()
 
   def compress(self, vol, slab_shape, markov_model_order: int = 0, allow_pins: bool = False, fortran_order: bool = True, defer: bool = False):
-    """Every rank passes its own z-slab (slab_shape = (sx, sy, sz_local)).  Returns the
-    stream of the whole volume on rank 0, None elsewhere.
+    """Every rank passes its own z-slab (slab_shape = (sx, sy, sz_local)): the slabs follow each other in rank
+    order, sz_local may differ from rank to rank and may be 0 (an empty `vol`), as long as one rank holds a slice.
+    Returns the stream of the whole volume on rank 0, None elsewhere.
     defer=True returns a callable instead, as soon as this rank's slab stream is complete in HBM: with a
     backend whose crack codes travel to the host in the background (HipBackend.async_host_copy) the
     caller can decode from the resident stream meanwhile; calling it waits for the copy, joins the
@@ -617,13 +650,22 @@ class ShardedCodec:
 
     sx, sy, sz = slab_shape
     voxels_local = sx * sy * sz
+    # A rank without slices (sz_local = 0) joins every collective with an empty contribution and never hands the
+    # backend an empty volume: the encoder answers that with a bare header, without the exchange of unique labels
+    # the other ranks would be waiting in.
+    idle = voxels_local == 0
     # 1. whole-volume reductions: pixel_pairs (linear, crosses slab boundaries) and max label
-    mx, pairs, first, last = be.stats(vol, slab_shape)
+    mx, pairs, first, last = (0, 0, 0, 0) if idle else be.stats(vol, slab_shape)
     # uint64 labels travel as their int64 bit patterns (labels >= 2^63 do not fit torch.int64 as values)
     mine_np = np.array([pairs, mx, first, last, voxels_local], dtype=np.uint64).view(np.int64)
     table = self._gather_rows(mine_np).view(np.uint64)
     tot_pairs = int(table[:, 0].sum())
     nonempty = [r for r in range(self.world) if table[r, 4] > 0]
+    if not nonempty:
+      raise ValueError("sharded compress: no rank holds a slice")      # (every rank sees the same table)
+    # header, model, unique list and pin section are written by the first rank that holds slices: its slab stream
+    # has a header and a model, and its backend a session, whichever ranks are empty (rank 0 included)
+    lead = nonempty[0]
     for a, b in zip(nonempty[:-1], nonempty[1:]):
       tot_pairs += int(table[a, 3] == table[b, 2])     # the pair straddling a slab boundary
     tot_voxels = int(table[:, 4].sum())
@@ -638,7 +680,7 @@ class ShardedCodec:
     # 2. one markov model for all slabs
     order = int(markov_model_order)
     if order > 0:
-      hist = be.markov_hist(vol, slab_shape, crack_format, order)
+      hist = np.zeros((4 ** order) * 4, dtype=np.uint32) if idle else be.markov_hist(vol, slab_shape, crack_format, order)
       h = torch.from_numpy(hist.astype(np.int64)).to(self.device)
       dist.all_reduce(h, op=dist.ReduceOp.SUM)
       hist = h.cpu().numpy()
@@ -700,11 +742,15 @@ class ShardedCodec:
         return out
       overrides["merge_unique"] = _merge_unique
     direct = hasattr(be, "codes_to_host")      # the crack codes go from HBM straight to their place in the shared buffer
-    if direct:
+    if direct and not idle:
       be.defer_codes(slab_shape, be.itemsize(vol), True)
     try:
       try:
-        slab = be.encode(vol, slab_shape, False, fortran_order, order, overrides)
+        if idle:
+          # the exchange the other ranks enter from their encoder's callback, with an empty list
+          uniq_idle = _merge_unique(np.zeros(0, np.uint64)) if early_merge else np.zeros(0, np.uint64)
+        else:
+          slab = be.encode(vol, slab_shape, False, fortran_order, order, overrides)
       except Exception as exc:
         if not early_merge:
           raise
@@ -715,12 +761,16 @@ class ShardedCodec:
         self._legacy_merge = True
         early_merge = False
         overrides.pop("merge_unique", None)
-        slab = be.encode(vol, slab_shape, False, fortran_order, order, overrides)
+        if idle:
+          uniq_idle = np.zeros(0, np.uint64)
+        else:
+          slab = be.encode(vol, slab_shape, False, fortran_order, order, overrides)
     finally:
-      if direct:
+      if direct and not idle:
         be.defer_codes(slab_shape, be.itemsize(vol), False)
     mark("encode")
-    sec = _SlabSections(slab)
+    sec = _SlabSections.empty(sx, sy, overrides["stored_width"], uniq_idle) if idle else _SlabSections(slab)
+    model_bytes = 0 if order == 0 else ((4 ** order) * 5 + 4) // 8      # header.hpp:284-297; the same on every rank
     mark("sections")
     dev = self.device
     table = self._gather_rows(np.array([len(sec.uniq), sec.n_keys, len(sec.cracks), sec.sz], dtype=np.int64))
@@ -768,10 +818,10 @@ class ShardedCodec:
     rows_done = False
     if use_pins and hasattr(be, "pins_rows_first") and not _os3.environ.get("CKL_PINS_ON_ROOT"):
       # every rank works on its own rows of the whole volume; rank 0 only writes the section
-      got = self._pins_by_rows(be, vol, slab_shape, table, sec, cw, sw, mark)
+      got = self._pins_by_rows(be, vol, slab_shape, table, sec, cw, sw, mark, lead)
       if got is not None:
         rows_done = True
-        pins_section = got if self.rank == 0 else None
+        pins_section = got if self.rank == lead else None
     if rows_done:
       pass
     elif use_pins and hasattr(be, "pin_labels_device"):
@@ -785,18 +835,18 @@ class ShardedCodec:
       id_base = int(table[:self.rank, 1].sum())
       sxy = sx * sy
       cc_mine = torch.empty(max(sxy * sec.sz, 1), dtype=torch.int32, device=vol.device)
-      nc_mine = be.components_device(vol, slab_shape, id_base, cc_mine)
+      nc_mine = np.zeros(0, np.uint32) if idle else be.components_device(vol, slab_shape, id_base, cc_mine)
       if not np.array_equal(nc_mine.astype(np.int64), ncomp_mine):
         raise RuntimeError("component counts of the slab stream and of the component pass differ")
       counts = [int(table[r, 3]) * sxy for r in range(self.world)]
-      lab_all = self._collect_on_root(vol.reshape(-1), counts)
-      cc_all = self._collect_on_root(cc_mine[:sxy * sec.sz], counts)
+      lab_all = self._collect_on_root(vol.reshape(-1), counts, lead)
+      cc_all = self._collect_on_root(cc_mine[:sxy * sec.sz], counts, lead)
       max_sz = max(int(table[:, 3].max()), 1)
       nc_pad = torch.zeros(max_sz, dtype=torch.int64, device=dev)
       nc_pad[:sec.sz] = torch.from_numpy(nc_mine.astype(np.int64)).to(dev)
       nc_every = [torch.empty_like(nc_pad) for _ in range(self.world)]
       dist.all_gather(nc_every, nc_pad)
-      if self.rank == 0:
+      if self.rank == lead:
         nc_all = np.concatenate([nc_every[r][:int(table[r, 3])].cpu().numpy() for r in range(self.world)]).astype(np.uint32)
         pins_section = be.pin_labels_device(lab_all, cc_all, (sx, sy, sz_tot), nc_all, sw)
         del lab_all, cc_all
@@ -819,16 +869,17 @@ class ShardedCodec:
       cc_all = big[cc_off:cc_off + sxy * sz_tot * 4].view(np.uint32)
       nc_all = big[nc_off:nc_off + 4 * sz_tot].view(np.uint32)
       mine = slice(sxy * z_before, sxy * (z_before + sec.sz))
-      be.volume_to_host(vol, lab_all[mine])
       nc_mine = np.zeros(sec.sz, dtype=np.uint32)
       cc_mine = np.zeros(sxy * sec.sz, dtype=np.uint32)
-      be.components(vol, slab_shape, id_base, cc_mine, nc_mine)
+      if not idle:
+        be.volume_to_host(vol, lab_all[mine])
+        be.components(vol, slab_shape, id_base, cc_mine, nc_mine)
       if not np.array_equal(nc_mine.astype(np.int64), ncomp_mine):
         raise RuntimeError("component counts of the slab stream and of the component pass differ")
       cc_all[mine] = cc_mine
       nc_all[z_before:z_before + sec.sz] = nc_mine
       dist.barrier()
-      if self.rank == 0:
+      if self.rank == lead:
         L = _lib.lib()
         out_p, out_n = C.c_void_p(), C.c_uint64()
         rc = L.ckl_pin_labels_host(lab_all.ctypes.data, item, cc_all.ctypes.data, sx, sy, sz_tot, nc_all.ctypes.data,
@@ -839,7 +890,7 @@ class ShardedCodec:
         L.ckl_free(out_p)
     if use_pins:
       n_pin = torch.tensor([0 if pins_section is None else len(pins_section)], dtype=torch.int64, device=dev)
-      dist.broadcast(n_pin, src=0)
+      dist.broadcast(n_pin, src=lead)
       label_bytes = int(n_pin.item())
       kw = 1
       mark("pins")
@@ -851,7 +902,7 @@ class ShardedCodec:
     o_comp = o_labels + 8 + n_merged * sw
     o_keys = o_comp + sz_tot * cw
     o_model = o_labels + label_bytes
-    o_cracks = o_model + len(sec.model)
+    o_cracks = o_model + model_bytes
     o_tail = o_cracks + int(table[:, 2].sum())
     total = o_tail + 4 * (sz_tot + 1)
     keys_before = int(table[:self.rank, 1].sum())
@@ -866,7 +917,7 @@ class ShardedCodec:
     base = C.addressof(C.c_ubyte.from_buffer(self._shared.mm))
     # the big host copies first: the re-keying above is still running on the device
     out[o_zidx + 4 * z_before: o_zidx + 4 * (z_before + sec.sz)] = sec.zidx
-    if direct:
+    if direct and not idle:      # (a rank without slices has no session to ask, and nothing to place)
       got = be.codes_to_host(base + o_cracks + cracks_before, len(sec.cracks))
       if got != len(sec.cracks):
         raise RuntimeError("crack code bytes of the slab stream and of the encoder session differ")
@@ -885,7 +936,7 @@ class ShardedCodec:
       # the label section's crc32c is put together from the ranks' own parts (ckl_crc32c_combine)
       part = np.array([L.ckl_crc32c(base + c_at, c_len), c_len, L.ckl_crc32c(base + k_at, k_len), k_len], dtype="<u4")
       out[o_part + 16 * self.rank: o_part + 16 * (self.rank + 1)] = part.view(np.uint8)
-    if self.rank == 0:
+    if self.rank == lead:
       if use_pins:
         out[o_labels:o_labels + label_bytes] = pins_section
       else:
@@ -922,6 +973,8 @@ class ShardedCodec:
       labels_crc = int(L.ckl_crc32c(base + o_labels, o_comp - o_labels))        # count + unique labels
       for col in (0, 2):                                                          # component counts, then keys, in rank order
         for r in range(self.world):
+          if not int(parts[r, col + 1]):
+            continue      # a rank without slices (or without keys) adds no byte
           labels_crc = int(L.ckl_crc32c_combine(labels_crc, int(parts[r, col]), int(parts[r, col + 1])))
     out[o_tail:o_tail + 4] = np.frombuffer(labels_crc.to_bytes(4, "little"), dtype=np.uint8)
     mark("crc")
@@ -931,12 +984,15 @@ class ShardedCodec:
     return SharedStream(self._shared.mm, total)
 
   # -- pins, sharded by rows ------------------------------------------------------
-  def _rows_of(self, sy: int):
-    """[(y0, rows)] of every rank: the rows dealt out as evenly as they go (the first ranks take the remainder)."""
-    base, rem = divmod(int(sy), self.world)
+  def _rows_of(self, sy: int, holders=None):
+    """[(y0, rows)] of every rank: the rows dealt out as evenly as they go (the first ranks take the remainder) among
+    `holders`, the ranks that hold slices (default: all).  A rank without slices has no encoder session for the
+    row passes and gets no rows."""
+    holders = list(range(self.world)) if holders is None else list(holders)
+    base, rem = divmod(int(sy), len(holders))
     out, y = [], 0
     for r in range(self.world):
-      n = base + (1 if r < rem else 0)
+      n = (base + (1 if holders.index(r) < rem else 0)) if r in holders else 0
       out.append((y, n))
       y += n
     return out
@@ -999,7 +1055,7 @@ class ShardedCodec:
     except Exception as exc:      # noqa: BLE001 (whatever it is, the other ranks must hear of it)
       return exc
 
-  def _pins_by_rows(self, be, vol, slab_shape, table, sec, cw, sw, mark):
+  def _pins_by_rows(self, be, vol, slab_shape, table, sec, cw, sw, mark, lead=0):
     """The pin label section with every rank working on its own ROWS of the whole volume (ckl_pins_rows_*,
     include/crackle_amd.h): labels and component ids are transposed from z-slabs to row slabs, the per-component
     extrema are reduced over the ranks between the device passes, rank 0 writes the section (ordered cover).
@@ -1017,12 +1073,15 @@ class ShardedCodec:
     cc_mine = torch.empty(max(sxy * sec.sz, 1), dtype=torch.int32, device=dev)
     got = {}
     def _components():
+      if not sec.sz:      # a rank without slices has no components, and no session to ask
+        got["nc"] = np.zeros(0, np.uint32)
+        return
       got["nc"] = be.components_device(vol, slab_shape, id_base, cc_mine)
       if not np.array_equal(got["nc"].astype(np.int64), ncomp_mine):
         raise RuntimeError("component counts of the slab stream and of the component pass differ")
     self._agree(self._local(_components))      # before the transposes: a rank that raised would leave the others in all_to_all_single
     nc_mine = got["nc"]
-    rows = self._rows_of(sy)
+    rows = self._rows_of(sy, [r for r in range(self.world) if sz_list[r]])
     y0, nrows = rows[self.rank]
     lab_rows = self._to_row_slabs(vol.reshape(sec.sz, sy, sx), sz_list, rows)
     cc_rows = self._to_row_slabs(cc_mine[:sxy * sec.sz].view(sec.sz, sy, sx), sz_list, rows)
@@ -1066,20 +1125,20 @@ class ShardedCodec:
     nc_pad[:sec.sz] = torch.from_numpy(nc_mine.astype(np.int64)).to(self.device)
     nc_every = [torch.empty_like(nc_pad) for _ in range(self.world)]
     dist.all_gather(nc_every, nc_pad)
-    if self.rank != 0:
+    if self.rank != lead:
       return np.zeros(0, np.uint8)
     nc_all = np.concatenate([nc_every[r][:sz_list[r]].cpu().numpy() for r in range(self.world)]).astype(np.uint32)
     section = be.pins_rows_section(sx, sy, sz_tot, N, nc_all, comp_label, first_any, choice, ze, offsets, ids, sw)
     mark("pins:section")
     return section
 
-  def _collect_on_root(self, mine: torch.Tensor, counts):
-    """Concatenates every rank's 1-D device tensor (counts[r] elements, rank order) in rank 0's
-    device memory with point-to-point transfers: device to device when the process group carries
-    device tensors (RCCL over xGMI), through host staging otherwise (gloo).  None off rank 0."""
+  def _collect_on_root(self, mine: torch.Tensor, counts, root: int = 0):
+    """Concatenates every rank's 1-D device tensor (counts[r] elements, rank order) in the device memory of
+    `root` (the first rank that holds slices) with point-to-point transfers: device to device when the process
+    group carries device tensors (RCCL over xGMI), through host staging otherwise (gloo).  None off `root`."""
     import os
-    if os.environ.get("CKL_TEST_NO_COLLECT"):      # testing: the pin stage must not fall back to the collection on rank 0
-      raise RuntimeError("the whole volume was asked for on rank 0 (CKL_TEST_NO_COLLECT)")
+    if os.environ.get("CKL_TEST_NO_COLLECT"):      # testing: the pin stage must not fall back to the collection on one rank
+      raise RuntimeError("the whole volume was asked for on one rank (CKL_TEST_NO_COLLECT)")
     direct = self.device.type == mine.device.type
     # the unsigned 16 / 32 / 64-bit dtypes have no entry in the collective backends' type tables: the
     # labels travel as the signed type of the same width (bit patterns; the caller gets `mine`'s dtype back)
@@ -1090,17 +1149,18 @@ class ShardedCodec:
     if orig_dtype in as_signed:
       mine = mine.view(as_signed[orig_dtype])
       counts = [c * scale for c in counts]
-    if self.rank != 0:
+    if self.rank != root:
       if counts[self.rank]:
-        dist.send(mine.contiguous() if direct else mine.to(self.device), dst=0)
+        dist.send(mine.contiguous() if direct else mine.to(self.device), dst=root)
       return None
     whole = torch.empty(max(sum(counts), 1), dtype=mine.dtype, device=mine.device)
-    whole[:counts[0]] = mine
-    off = counts[0]
-    for r in range(1, self.world):
+    off = 0
+    for r in range(self.world):
       if not counts[r]:
         continue
-      if direct:
+      if r == root:
+        whole[off:off + counts[r]] = mine
+      elif direct:
         dist.recv(whole[off:off + counts[r]], src=r)
       else:
         stage = torch.empty(counts[r], dtype=mine.dtype, device=self.device)
@@ -1111,16 +1171,30 @@ class ShardedCodec:
 
   # -- decode -------------------------------------------------------------------
   def open_decoder(self, binary: Optional[bytes], slab_shape):
-    """Makes the stream resident on every rank (broadcast from rank 0) and returns a
-    session that decodes this rank's z-range into a caller-provided volume."""
-    if self.world > 1 or self.force_sharded:
-      n = torch.tensor([len(binary) if self.rank == 0 else 0], dtype=torch.int64, device=self.device)
-      dist.broadcast(n, src=0)
-      if self.rank == 0:
-        buf = torch.frombuffer(bytearray(bytes(binary)), dtype=torch.uint8).to(self.device)
-      else:
-        buf = torch.empty(int(n.item()), dtype=torch.uint8, device=self.device)
-      dist.broadcast(buf, src=0)
-      binary = bytes(buf.cpu().numpy().tobytes())
-    sz = slab_shape[2]
-    return self.backend.open_decoder(binary, self.rank * sz, (self.rank + 1) * sz)
+    """Makes the stream resident on every rank (broadcast from rank 0) and returns a session that decodes this
+    rank's z-range into a caller-provided volume.  slab_shape = (sx, sy, sz_local) of THIS rank: the depths may
+    differ from rank to rank, zero included; rank r decodes the slices behind those of the ranks before it.  The
+    depths must add up to the stream's sz (ValueError on every rank otherwise).  A rank of depth 0 gets a session
+    whose run() accepts an empty output and writes nothing."""
+    sz = int(slab_shape[2])
+    if not (self.world > 1 or self.force_sharded):
+      return self.backend.open_decoder(binary, 0, sz)
+    # one gather carries the stream's length (rank 0 has it) and every rank's depth
+    table = self._gather_rows(np.array([len(binary) if self.rank == 0 else 0, sz], dtype=np.int64))
+    n = int(table[0, 0])
+    if self.rank == 0:
+      buf = torch.frombuffer(bytearray(bytes(binary)), dtype=torch.uint8).to(self.device)
+    else:
+      buf = torch.empty(n, dtype=torch.uint8, device=self.device)
+    dist.broadcast(buf, src=0)
+    binary = bytes(buf.cpu().numpy().tobytes())
+    info = _lib.HeaderInfo()
+    if _lib.lib().ckl_header_info_from_bytes(binary[:64], min(len(binary), 64), info) != _lib.CKL_OK:
+      raise RuntimeError(_lib.last_error())
+    depths = [int(d) for d in table[:, 1]]
+    if min(depths) < 0 or sum(depths) != int(info.sz):      # the same verdict on every rank: all of them hold the table and the stream
+      raise ValueError(f"sharded decode: the ranks' depths {tuple(depths)} do not add up to the stream's {int(info.sz)} slices")
+    z0 = sum(depths[:self.rank])
+    if sz == 0:
+      return _NoSlicesSession()
+    return self.backend.open_decoder(binary, z0, z0 + sz)

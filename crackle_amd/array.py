@@ -6,7 +6,7 @@ crosses the link.  paste() is the way back (the reference's __setitem__, crackle
 the slices of the box's z-range are decoded, edited and encoded again in HBM (ckl_paste)."""
 import ctypes as C
 import operator
-from typing import Optional, Union
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -288,7 +288,10 @@ class CrackleArray:
   def dilate(self, connectivity: int = 26) -> "CrackleArray":
     return CrackleArray(operations.dilate(self.binary, connectivity=connectivity, device=self.device), self.device)
 
-  def opening(self, connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":
+  def downsample(self, factor: Tuple[int, int, int] = (2, 2, 1), num_mips: int = 1) -> List["CrackleArray"]:
+    return [CrackleArray(b, self.device) for b in operations.downsample(self.binary, factor=factor, num_mips=num_mips, device=self.device)]
+
+  def opening(self,connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":
     return CrackleArray(operations.opening(self.binary, connectivity=connectivity, erode_border=erode_border, device=self.device), self.device)
 
   def closing(self, connectivity: int = 26, erode_border: bool = True) -> "CrackleArray":

@@ -1,7 +1,8 @@
 // crackle.operations.recompress (crackle/operations.py:664-857 decodes slabs to voxels and compresses them again), and
-// erode and dilate, which are the same road with another volume at its end.  Here no voxel exists anywhere: a TABLES run
-// of the decoder leaves the runs of every slice and the label of every component, a plane stage writes the encoder's
-// planes and their counts from them (plain: ckl_recompress.hpp, eroded: ckl_erode.hpp, dilated: ckl_dilate.hpp), and
+// erode, dilate and downsample, which are the same road with another volume at its end.  Here no voxel exists anywhere:
+// a TABLES run of the decoder leaves the runs of every slice and the label of every component, a plane stage writes the
+// encoder's planes and their counts from them (plain: ckl_recompress.hpp, eroded: ckl_erode.hpp, dilated:
+// ckl_dilate.hpp, pooled: ckl_downsample.hpp, the one whose volume has another shape than the decoder's), and
 // encode_from_planes (ckl_encoder.hpp) goes on as the encoder does from cached planes, with its label stage reading the
 // same tables.  The bytes are those of compress(edit(decompress(stream)), markov_model_order).
 #include "ckl_encoder.hpp"
@@ -9,6 +10,7 @@
 #include "ckl_recompress.hpp"
 #include "ckl_erode.hpp"
 #include "ckl_dilate.hpp"
+#include "ckl_downsample.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -20,9 +22,10 @@ namespace {
 
 // what a call does to the labels on their way through
 struct LabelEdit {
-	enum Kind { NONE, ERODE, DILATE } kind = NONE;
+	enum Kind { NONE, ERODE, DILATE, POOL } kind = NONE;
 	int connectivity = 0;          // ERODE, DILATE: 6, 18, 26
 	bool keep_border = false;      // ERODE: neighbours outside the volume are ignored
+	int fx = 1, fy = 1, fz = 1;    // POOL: (2, 2, 1) or (2, 2, 2)
 };
 
 // per kind: the operation's name, and the two fields of its CKL_PROFILE line that carry the kind in their names
@@ -31,6 +34,7 @@ constexpr EditNames kEditNames[] = {
 	{ "recompress", "label_planes", "k_label_planes_from_runs_device" },
 	{ "erode", "keep_planes", "k_erode_device" },
 	{ "dilate", "gain_planes", "k_dilate_device" },
+	{ "downsample", "pool_planes", "k_pool_device" },
 };
 
 // Device scratch of one call's edit.  What a plane stage returns points into it and is read by the encoder's label
@@ -40,6 +44,9 @@ struct EditScratch {
 	DevBuf<uint32_t> dilate_nonzero_gain;      // ckl_dilate.hpp's planes N | gain, [nslices][plane_words] each
 	DevBuf<uint64_t> dilate_gain_off;          // [nslices][plane_words]
 	DevBuf<uint64_t> dilate_gain_label;        // [gained]
+	DevBuf<uint32_t> pool_cut;                 // ckl_downsample.hpp's plane of cuts, [osz][output plane_words]
+	DevBuf<uint64_t> pool_cut_off;             // [osz][output plane_words]
+	DevBuf<uint64_t> pool_label;               // [cuts]
 };
 
 // what the plane stages launch with
@@ -47,9 +54,9 @@ struct Road {
 	ckl_decoder& d;                    // after its TABLES run
 	ckl_encoder& e;                    // planes_adopt() done: the stages write plane_v / plane_h and d_count_vh [3][ns]
 	hipStream_t s;                     // the encode session's
-	uint32_t ns;
-	dim3 word_grid;                    // a thread per 32-pixel word
-	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's cursor
+	uint32_t ns;                       // the ENCODER's slices (POOL: not the decoder's)
+	dim3 word_grid;                    // a thread per 32-pixel word of the encoder's planes
+	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's and ckl_downsample's cursor
 };
 
 // the decode session's tables as the kernels of this road read them
@@ -65,7 +72,7 @@ RunLabels run_labels(const ckl_decoder& d) {
 // one label per run, at the runs' own bases (in PAINT's scratch of the decode session): what erode and dilate read
 const uint64_t* gather_run_labels(const Road& r, const RunLabels& src) {
 	r.d.d_run_label.ensure(r.d.rtot);
-	hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((r.d.max_rcap + kBlock - 1) / kBlock + 1, 256), r.ns), dim3(kBlock), 0, r.s, src, r.d.d_run_label.p);
+	hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((r.d.max_rcap + kBlock - 1) / kBlock + 1, 256), r.d.nslices), dim3(kBlock), 0, r.s, src, r.d.d_run_label.p);
 	return r.d.d_run_label.p;
 }
 
@@ -106,6 +113,23 @@ unsigned long long dilated_planes(const Road& r, RunLabels& src, const uint64_t*
 	return gained;
 }
 
+// Returns the number of cuts and leaves the pooled triple in src; counters[0] takes the largest pooled label.  The word
+// grid, the planes and the counts are the pooled volume's, the tables behind src are the input's.
+unsigned long long pooled_planes(const Road& r, RunLabels& src, const uint64_t* run_label, const PoolGeom& p, EditScratch& scratch) {
+	const size_t pw = p.plane_words * r.ns;
+	scratch.pool_cut.ensure(pw);
+	scratch.pool_cut_off.ensure(pw);
+	hipLaunchKernelGGL(k_pool_cuts, r.word_grid, dim3(kBlock), 0, r.s, src.g, p, scratch.pool_cut.p, scratch.pool_cut_off.p, r.counters + 1);
+	const unsigned long long cuts = download(r.counters + 1, 1, r.s)[0];      // the host sizes the pooled runs' labels (every word has a cut: not 0)
+	scratch.pool_label.ensure(cuts);
+	if (p.fz == 1u) hipLaunchKernelGGL(k_pool_labels<1>, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, p, scratch.pool_cut.p, scratch.pool_cut_off.p, scratch.pool_label.p, r.counters);
+	else hipLaunchKernelGGL(k_pool_labels<2>, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, p, scratch.pool_cut.p, scratch.pool_cut_off.p, scratch.pool_label.p, r.counters);
+	src.pool_cut = scratch.pool_cut.p; src.pool_off = scratch.pool_cut_off.p; src.pool_label = scratch.pool_label.p;
+	src.pool_sx = p.sx; src.pool_sy = p.sy; src.pool_row_words = p.row_words; src.pool_plane_words = p.plane_words;
+	hipLaunchKernelGGL(k_pool_planes, r.word_grid, dim3(kBlock), 0, r.s, src, p, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
+	return cuts;
+}
+
 // lib::pixel_pairs (lib.hpp:249-256): equal neighbours in x-fastest order — inside the rows every pair that V does not
 // mark, and the wrap-arounds the plane writer counted.  counts: [3][ns] bits of V | bits of H | wrap pairs
 VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_label, int64_t sx, int64_t sy, uint32_t ns) {
@@ -115,8 +139,9 @@ VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_
 	return st;
 }
 
-// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the three operations read it)
-void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, const ckl_encoder& e, float ms_kernel, unsigned long long gained) {
+// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the four operations read it).  extra: DILATE's
+// gained pixels, POOL's pieces
+void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, const ckl_encoder& e, float ms_kernel, unsigned long long extra) {
 	double graph = 0, cracks = 0, labels = 0, assembly = 0;
 	for (const auto& m : e.host_marks) {
 		const std::string name = m.first;
@@ -127,7 +152,8 @@ void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, co
 	}
 	const EditNames& names = kEditNames[edit.kind];
 	char tail[40] = "";
-	if (edit.kind == LabelEdit::DILATE) snprintf(tail, sizeof(tail), " gained=%llu", gained);
+	if (edit.kind == LabelEdit::DILATE) snprintf(tail, sizeof(tail), " gained=%llu", extra);
+	if (edit.kind == LabelEdit::POOL) snprintf(tail, sizeof(tail), " pieces=%llu", extra);
 	fprintf(stderr, "[ckl %s host ms] tables=%.2f %s=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f %s=%.3f%s\n",
 		names.op, ms_tables, names.planes_field, ms_planes, graph, cracks, labels, assembly, names.device_field, ms_kernel, tail);
 }
@@ -135,7 +161,11 @@ void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, co
 // What the host refuses, before any device is asked for: the stream's header and the markov order of the output
 // (markov_order < 0: the stream's own).
 Header checked_header(const uint8_t* buf, uint64_t n, int markov_order, const LabelEdit& edit, uint64_t& order) {
-	if (edit.kind != LabelEdit::NONE && edit.connectivity != 6 && edit.connectivity != 18 && edit.connectivity != 26)
+	if (edit.kind == LabelEdit::POOL) {
+		if (edit.fx != 2 || edit.fy != 2 || (edit.fz != 1 && edit.fz != 2))
+			throw Error(CKL_ERR_ARG, "crackle_amd: downsample: factor must be (2, 2, 1) or (2, 2, 2). Got: (" + std::to_string(edit.fx) + ", " + std::to_string(edit.fy) + ", " + std::to_string(edit.fz) + ")");
+	}
+	else if (edit.kind != LabelEdit::NONE && edit.connectivity != 6 && edit.connectivity != 18 && edit.connectivity != 26)
 		throw Error(CKL_ERR_ARG, std::string("crackle_amd: ") + kEditNames[edit.kind].op + ": connectivity must be 6, 18 or 26. Got: " + std::to_string(edit.connectivity));
 	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
 	const Header head = Header::parse(buf, n);
@@ -163,7 +193,9 @@ double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono
 void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, const LabelEdit& edit, uint8_t** out, uint64_t* out_len) {
 	uint64_t order = 0;
 	const Header head = checked_header(buf, n, markov_order, edit, order);
-	const int64_t sx = head.sx, sy = head.sy, sz = head.sz;
+	// the encoder's volume: the decoder's, or the pooled one (an axis of size 0 or 1 keeps its size)
+	const bool pool = edit.kind == LabelEdit::POOL;
+	const int64_t sx = pool ? (head.sx + 1) / 2 : head.sx, sy = pool ? (head.sy + 1) / 2 : head.sy, sz = pool && edit.fz == 2 ? (head.sz + 1) / 2 : head.sz;
 	if (head.voxels() == 0) {
 		hand_out(header_bytes(stream_header(head.data_width, sx, sy, sz, VolumeStats(), false, head.fortran_order, order, nullptr)), OutAlloc::MALLOC, out, out_len);
 		return;
@@ -183,20 +215,24 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, co
 	const EncoderPtr enc(raw);
 	ckl_encoder& e = *enc;
 	enter(&e);
-	const uint32_t ns = d.nslices;
-	planes_adopt(e, d.row_words, d.plane_words, ns, 3);
+	const uint32_t ns = static_cast<uint32_t>(sz);
+	const uint32_t row_words = static_cast<uint32_t>((sx + 31) / 32);
+	const uint64_t plane_words = static_cast<uint64_t>(row_words) * sy;
+	planes_adopt(e, row_words, plane_words, ns, 3);
 	counters.ensure(2);
 	CKL_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), e.stream));
-	const Road r = { d, e, e.stream, ns, dim3(static_cast<uint32_t>((d.plane_words + kBlock - 1) / kBlock), ns), counters.p };
+	const Road r = { d, e, e.stream, ns, dim3(static_cast<uint32_t>((plane_words + kBlock - 1) / kBlock), ns), counters.p };
 	CKL_HIP(hipEventRecord(e.evd0, r.s));
 	const uint64_t* run_label = edit.kind == LabelEdit::NONE ? nullptr : gather_run_labels(r, src);
 	unsigned long long gained = 0;
 	if (edit.kind == LabelEdit::ERODE) src.keep = eroded_planes(r, src, run_label, edit, scratch);
 	else if (edit.kind == LabelEdit::DILATE) gained = dilated_planes(r, src, run_label, edit, scratch);
+	else if (pool) pooled_planes(r, src, run_label, { static_cast<uint32_t>(edit.fz), d.nslices, static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), row_words, plane_words }, scratch);
 	else plain_planes(r, src);
 	CKL_HIP(hipEventRecord(e.evd1, r.s));
-	// (k_erode_keep has taken the largest surviving label; dilation leaves the largest label what it was)
-	if (edit.kind != LabelEdit::ERODE) hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, r.s,
+	// (k_erode_keep has taken the largest surviving label, k_pool_labels the largest pooled one; dilation leaves the
+	// largest label what it was)
+	if (edit.kind != LabelEdit::ERODE && !pool) hipLaunchKernelGGL(k_label_map_max, dim3(static_cast<uint32_t>(std::min<uint64_t>((d.total_comp + kBlock - 1) / kBlock + 1, 1024))), dim3(kBlock), 0, r.s,
 		d.d_label_map.p, d.total_comp, counters.p);
 	const std::vector<uint32_t> counts = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), r.s);
 	const VolumeStats st = stats_from_counts(counts, download(counters.p, 1, r.s)[0], sx, sy, ns);
@@ -205,7 +241,10 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, co
 	const auto t_planes = Clock::now();
 
 	encode_from_planes(e, src, sx, sy, sz, head.data_width, head.fortran_order, order, st, counts, out, out_len);
-	if (getenv("CKL_PROFILE")) print_profile(edit, ms_between(t_start, t_tables), ms_between(t_tables, t_planes), e, ms_kernel, gained);
+	// POOL's pieces: the pooled volume's runs, one per row and one more per bit of V (of the cuts, those that changed the label)
+	unsigned long long pieces = static_cast<unsigned long long>(sy) * ns;
+	for (uint32_t zi = 0; zi < ns; zi++) pieces += counts[zi];
+	if (getenv("CKL_PROFILE")) print_profile(edit, ms_between(t_start, t_tables), ms_between(t_tables, t_planes), e, ms_kernel, pool ? pieces : gained);
 }
 
 }  // namespace
@@ -232,6 +271,16 @@ int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int 
 		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
 		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: dilate: flags must be 0");
 		recompress(buf, n, markov_model_order, device, { LabelEdit::DILATE, connectivity, false }, out, out_len);
+	});
+}
+
+int ckl_downsample(const uint8_t* buf, uint64_t n, int fx, int fy, int fz, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: downsample: flags must be 0");
+		LabelEdit edit;
+		edit.kind = LabelEdit::POOL; edit.fx = fx; edit.fy = fy; edit.fz = fz;
+		recompress(buf, n, markov_model_order, device, edit, out, out_len);
 	});
 }
 

@@ -32,6 +32,15 @@ struct RunLabels {
 	const uint32_t* gain = nullptr;
 	const uint64_t* gain_off = nullptr;
 	const uint64_t* gain_label = nullptr;
+	// ckl_downsample.hpp: the encoder's volume is the pooled one, of another shape than the decoder's.  pool_cut
+	// [osz][pool_plane_words]: bit x set where pixel x of the word's row may change its pooled label (bit 0 of every word
+	// is set); the pixel carries pool_label[pool_off[its word] + the set bits of the word at or below it - 1] (nullptr: no
+	// pooling, the encoder's volume has the decoder's shape)
+	const uint32_t* pool_cut = nullptr;
+	const uint64_t* pool_off = nullptr;
+	const uint64_t* pool_label = nullptr;
+	uint32_t pool_sx = 0, pool_sy = 0, pool_row_words = 0;
+	uint64_t pool_plane_words = 0;
 
 	// the labels of one slice's runs, the slice's bases fetched once; everything read from the tables is clamped as
 	// k_paint_window clamps it
@@ -59,6 +68,11 @@ struct RunLabels {
 		if (!(gw & bit)) return false;
 		l = gain_label[gain_off[at] + __popc(gw & (bit - 1u))];
 		return true;
+	}
+	// the pooled label of pixel (x, y) of slice zi of the POOLED volume (pool_cut is not null)
+	__device__ __forceinline__ uint64_t pooled(uint32_t zi, uint32_t x, uint32_t y) const {
+		const uint64_t at = zi * pool_plane_words + static_cast<uint64_t>(y) * pool_row_words + (x >> 5);
+		return pool_label[pool_off[at] + __popc(pool_cut[at] & mask_le(x & 31u)) - 1u];
 	}
 	// the run of pixel (x, y) of slice zi
 	__device__ __forceinline__ uint32_t run_at(uint32_t zi, uint32_t x, uint32_t y) const {
@@ -148,8 +162,9 @@ static __global__ void __launch_bounds__(kBlock) k_label_map_max(const uint64_t*
 }
 
 // One thread per component of the NEW planes: its first pixel (the strip path leaves it in the resolve's slots, the
-// run pipeline in comp_pix) -> the decoder's run at that pixel -> its label.  ncomp / comp_off / rbase_enc are the
-// ENCODER's.  grid = (ceil(most components of a slice / 256), nslices)
+// run pipeline in comp_pix) -> the decoder's run at that pixel -> its label; of a pooled volume (ckl_downsample.hpp),
+// whose slices have another shape than the decoder's, the pooled run at that pixel.  ncomp / comp_off / rbase_enc are
+// the ENCODER's, and so is the row length the pixel is split by.  grid = (ceil(most components of a slice / 256), nslices)
 static __global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
 	RunLabels t, const uint64_t* __restrict__ slots, uint32_t slot_cap, const uint32_t* __restrict__ comp_pix, const uint64_t* __restrict__ rbase_enc,
 	const uint32_t* __restrict__ ncomp, const uint64_t* __restrict__ comp_off, uint64_t* __restrict__ mapping
@@ -157,11 +172,14 @@ static __global__ void __launch_bounds__(kBlock) k_component_labels_from_runs(
 	const uint32_t zi = blockIdx.y;
 	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
 	if (c >= ncomp[zi]) return;
-	const uint32_t n_pixels = t.g.sx * t.g.sy;
+	// the slice of the ENCODER's volume: the pooled one's (ckl_downsample.hpp), otherwise the decoder's
+	const uint32_t sx = t.pool_cut ? t.pool_sx : t.g.sx, sy = t.pool_cut ? t.pool_sy : t.g.sy;
+	const uint32_t n_pixels = sx * sy;
 	uint32_t pix = slots ? static_cast<uint32_t>(slots[static_cast<uint64_t>(zi) * slot_cap + c]) : comp_pix[rbase_enc[zi] + c];
 	pix = pix < n_pixels ? pix : n_pixels - 1u;
-	const uint32_t y = pix / t.g.sx;
-	const uint32_t x = pix - y * t.g.sx;
+	const uint32_t y = pix / sx;
+	const uint32_t x = pix - y * sx;
+	if (t.pool_cut) { mapping[comp_off[zi] + c] = t.pooled(zi, x, y); return; }
 	const bool kept = !t.keep || ((t.keep[zi * t.g.plane_words + static_cast<uint64_t>(y) * t.g.row_words + (x >> 5)] >> (x & 31u)) & 1u);
 	uint64_t l;
 	if (!t.gained(zi, x, y, l)) l = kept ? t.label_of(zi, t.run_at(zi, x, y)) : 0ull;

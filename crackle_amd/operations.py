@@ -5,7 +5,7 @@ array_equal, mode_pooling_2x2x1, point_cloud, contacts, overlaps, connected_comp
 The label edits remap, mask and mask_except rewrite header and label section on the host; recompress
 re-encodes a stream from its own labels on the device (ckl_recompress), without decoding a voxel.  erode and dilate
 take the same road with the eroded or dilated labels at its end (ckl_erode, ckl_dilate); opening and closing are one
-after the other."""
+after the other.  downsample takes it with the pooled labels, and a smaller volume, at its end (ckl_downsample)."""
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -714,6 +714,56 @@ def dilate(
   matrix."""
   _checked_connectivity("dilate", connectivity)
   return _reencode("dilate", "ckl_dilate", binary, (int(connectivity), 0), markov_model_order, device)
+
+
+def downsample(
+  binary: bytes, factor: Tuple[int, int, int] = (2, 2, 1), num_mips: int = 1,
+  markov_model_order: Optional[int] = None, device: int = 0,
+) -> List[bytes]:
+  """A resolution pyramid of the stream: a list of num_mips streams, entry 0 the downsample of binary, entry k the
+  downsample of entry k - 1.  Each equals compress(pooled, markov_model_order=m), byte for byte, where pooled is the
+  level before it pooled by `factor`, in the input's dtype, without the voxels.  Level k has shape ceil(s / f) per
+  axis of level k - 1; an axis of size 0 or 1 keeps its size.
+
+  factor is (2, 2, 1) or (2, 2, 2).  Label 0 is an ordinary label in both rules.
+
+  (2, 2, 1) is the reference's rule (src/operations.hpp:1254-1293): with a, b, c, d at (x, y), (x + 1, y),
+  (x, y + 1), (x + 1, y + 1): a == b -> a, a == c -> a, b == c -> b, else d.  Where the block is cut by an odd sx or
+  sy, the voxel at its origin is copied.  So decompress(downsample(b)[0]) equals decompress(mode_pooling_2x2x1(b))
+  wherever the latter does not raise (it raises when its pooled slices pick different crack formats; this does not).
+
+  (2, 2, 2) takes the label that occurs most often among the block's voxels that exist: a block holds 8 voxels, or
+  4, 2 or 1 at odd ends.  Ties go to the smallest label, compared as unsigned 64-bit values: dilate()'s tie rule,
+  which does not depend on memory order.  At an odd sz the last output slice pools 2 x 2 x 1 blocks by this rule,
+  not by the reference's.
+
+  m is the input's order unless markov_model_order is given.  Every level has FLAT labels, format version 1,
+  whatever the input had (FLAT, pins, version 0), the input's data width and fortran_order flag, and the crack format
+  the pooled volume itself selects.
+
+  The levels are chained on the host, one device call each (ckl_downsample), with the stream crossing the host
+  between them; fusing them is not done.  On the device the decoder runs up to its run tables; no dense label volume
+  exists, neither the input's nor the pooled one: an output row can change its label only where one of the 2 * fz
+  input rows under it has a break, the rule is evaluated there with one label fetch per input run, the encoder's
+  planes are written from those pooled runs, and the encoder's crack and label stages follow for the pooled shape
+  (ckl_downsample.hpp).  Signed streams raise TypeError, another factor, num_mips < 1 or a negative order
+  ValueError; a damaged slice raises what decompress raises for it; a stream without voxels becomes the header-only
+  stream of the pooled shape, without a device.
+
+  Not done: other factors, a sparse mode that prefers non-zero labels, averaging."""
+  try:
+    f = tuple(int(v) for v in factor)
+  except (TypeError, ValueError):
+    f = ()
+  if f not in ((2, 2, 1), (2, 2, 2)):
+    raise ValueError(f"downsample: factor must be (2, 2, 1) or (2, 2, 2). Got: {factor}")
+  if int(num_mips) < 1:
+    raise ValueError(f"downsample: num_mips must be at least 1. Got: {num_mips}")
+  levels = []
+  for _ in range(int(num_mips)):
+    binary = _reencode("downsample", "ckl_downsample", binary, (*f, 0), markov_model_order, device)
+    levels.append(binary)
+  return levels
 
 
 def opening(

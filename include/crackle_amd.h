@@ -552,6 +552,27 @@ int ckl_erode(const uint8_t* buf, uint64_t n, int connectivity, int flags, int m
 int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int markov_model_order, int device,
                uint8_t** out, uint64_t* out_len);
 
+/* One level of a resolution pyramid (the reference has only mode_pooling_2x2x1's consumer): the stream that
+ * ckl_compress gives for the pooled volume, written as ckl_erode writes its own (FLAT labels, format version 1,
+ * markov_model_order < 0: keep the input's, the input's data width and fortran_order flag; the crack format is the
+ * one the pooled volume itself selects).  (fx, fy, fz) is (2, 2, 1) or (2, 2, 2); the output's shape is ceil(s / f)
+ * per axis, an axis of size 0 or 1 keeps its size.  Label 0 is an ordinary label.
+ *   (2, 2, 1)  the reference's rule (src/operations.hpp:1254-1293): with a, b, c, d at (x, y), (x + 1, y), (x, y + 1),
+ *              (x + 1, y + 1): a == b -> a, a == c -> a, b == c -> b, else d; where the block is cut by an odd sx or
+ *              sy, the voxel at its origin is copied.
+ *   (2, 2, 2)  the label that occurs most often among the block's voxels that exist (8, or 4, 2, 1 at odd ends); ties
+ *              go to the smallest label, compared as unsigned 64-bit values (ckl_dilate's tie rule).  At an odd sz the
+ *              last output slice pools 2 x 2 x 1 blocks by this rule, not by the reference's.
+ * No voxel is decoded and no dense label volume exists, neither the input's nor the pooled one: the decoder runs up to
+ * its run tables, the output words are cut where an input row under them has a break (k_pool_cuts), the rule is
+ * evaluated once per cut with one run cursor per input row (k_pool_labels), the encoder's planes are written from the
+ * pooled runs (k_pool_planes), and the encoder's crack and label stages follow for the OUTPUT's shape, the label stage
+ * reading the pooled runs.  `flags` must be 0.  FLAT, pin and version 0 streams; signed streams, another factor and
+ * flags other than 0 are CKL_ERR_ARG; a stream without voxels becomes the header-only stream of the output's shape,
+ * without a device.  A damaged slice fails as in ckl_decompress.  *out is released with ckl_free. */
+int ckl_downsample(const uint8_t* buf, uint64_t n, int fx, int fy, int fz, int flags, int markov_model_order, int device,
+                   uint8_t** out, uint64_t* out_len);
+
 /* Native form of crackle.operations.zsplit's range helper (crackle/operations.py:550-623):
  * the stream of slices [z_start, z_end) of a FLAT stream, without decoding (host only).
  * *out is released with ckl_free. */

@@ -7,18 +7,17 @@
 //                                                   src/crackcodes.hpp:128-281, 374-453  k_trail_* (ckl_trail.hpp)
 //   pack_codepoints / write_boc_index               src/crackcodes.hpp:318-372, 455-496  k_finish
 //   markov::gather_statistics / encode_markov       src/markov.hpp:193-220, 422-473      k_markov_hist / k_markov_pack
-//   cc3d::connected_components2d_4 + relabel        src/cc3d.hpp:114-144, 257-369        ckl_runs.hpp (runs of the label planes)
-//   labels::encode_flat                             src/labels.hpp:30-155      k_run_resolve (crc), k_mapping_comps + sort/unique
+//   cc3d::connected_components2d_4 + relabel        src/cc3d.hpp:114-144, 257-369        the flat label stage (ckl_encode_labels.hip)
+//   labels::encode_flat                             src/labels.hpp:30-155                the flat label stage (ckl_encode_labels.hip)
 //   stream assembly                                 src/crackle.hpp:171-216    host
-// crackle.operations.recompress without the voxels (ckl_recompress.hip) comes in through encode_from_planes; of its
-// kernels the label stage here launches k_component_labels_from_runs (ckl_recompress.hpp).
+// The flat label stage and the pin stage (ckl_encode_pins.hip) are units of their own; encode_typed here schedules them
+// against the crack trail.  crackle.operations.recompress without the voxels (ckl_recompress.hip) comes in through
+// encode_from_planes.
 #include "ckl_encoder.hpp"
+#include "ckl_encode_labels.hpp"
 #include "ckl_decoder.hpp"
-#include "ckl_runs.hpp"
-#include "ckl_strips.hpp"
 #include "ckl_trail.hpp"
 #include "ckl_code_words.hpp"
-#include "ckl_recompress.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -991,320 +990,6 @@ __global__ void __launch_bounds__(kBlock) k_markov_pack(
 	if (threadIdx.x == 0) payload_len[zi] = (carry + 7) / 8;
 }
 
-// ------------------------------------------------------------------------------
-// flat labels (labels.hpp:56-88): component -> label, read at the first pixel of every
-// component.  grid = (ceil(max components of a slice / 256), nslices)
-// ------------------------------------------------------------------------------
-// component -> label from the component's first pixel (k_run_assign leaves it in comp_pix): one thread per
-// component instead of one per run (C2: 1.6 M instead of 26 M)
-template <typename LABEL>
-__global__ void __launch_bounds__(kBlock) k_mapping_comps(
-	const LABEL* __restrict__ labels, RunArrays r, uint64_t sxy,
-	const uint64_t* __restrict__ comp_off, uint64_t* __restrict__ mapping
-) {
-	const uint32_t zi = blockIdx.y;
-	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-	if (c >= r.ncomp[zi]) return;
-	mapping[comp_off[zi] + c] = static_cast<uint64_t>(labels[zi * sxy + r.comp_pix[r.rbase[zi] + c]]);
-}
-
-// the encoder's strips (flat_enqueue): planes only, no record lists; seven workgroups per CU like k_strip_ccl
-// Tables of kEncStripCap runs, not kStripCap: the label stream runs beside two walks per CU and has kFlatResolveLds of
-// the CU's LDS (encode_typed: labels_at_walk).  Two of these workgroups fit into that, of the decoder's size only one:
-// at C2 (two walks of 58 KiB) the kernel took 0.79 ms with 2560 runs and the encode was slower than on the run pipeline;
-// with 2048, although the strips get 28 rows instead of 32, the encode's device time went from 2.72 to 2.56 ms.
-constexpr uint32_t kEncStripCap = 2048;
-constexpr size_t kFlatResolveLds = 40960;
-static_assert(2 * strip_ccl_words(kEncStripCap) * sizeof(uint32_t) <= kFlatResolveLds, "two strip workgroups beside two walks");
-__global__ void __launch_bounds__(kBlock, 7) k_strip_ccl_enc(RunGeom g, StripArrays sa, const uint32_t* __restrict__ G, uint32_t n_pixels) {
-	__shared__ __attribute__((aligned(16))) uint32_t s_lds[strip_ccl_words(kEncStripCap)];
-	strip_ccl_body<false, false, true, kEncStripCap>(g, sa, RecordLists{}, G, n_pixels, nullptr, blockIdx.y, blockIdx.x, s_lds);
-}
-
-// one thread per component: the slots of k_slice_resolve_enc -> the dense table (comp_off: the host's prefix of the
-// counts).  grid = (ceil(max components / kBlock), slices)
-__global__ void __launch_bounds__(kBlock) k_gather_slots(
-	const uint64_t* __restrict__ slots, uint32_t slot_cap, const uint32_t* __restrict__ ncomp, const uint64_t* __restrict__ comp_off, uint64_t* __restrict__ mapping
-) {
-	const uint32_t zi = blockIdx.y;
-	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-	if (c < ncomp[zi]) mapping[comp_off[zi] + c] = slots[static_cast<uint64_t>(zi) * slot_cap + c];
-}
-
-// Global component id of every voxel (cc3d.hpp:371-400 numbers components continuously
-// across slices) for the pin encoder: one thread per pixel, its run found by a popcount in
-// the row's break word, ids read from the run tables.  grid = (ceil(sxy / 256), nslices)
-__global__ void __launch_bounds__(kBlock) k_paint_components(
-	const uint32_t* __restrict__ planeV, uint32_t row_words, uint64_t plane_words, uint32_t sx, uint64_t sxy,
-	const uint32_t* __restrict__ word_base, const uint64_t* __restrict__ rbase, const uint32_t* __restrict__ run_cc,
-	const uint64_t* __restrict__ comp_off, uint32_t id_base, uint32_t* __restrict__ out
-) {
-	const uint32_t zi = blockIdx.y;
-	const uint32_t px = blockIdx.x * kBlock + threadIdx.x;
-	if (px >= sxy) return;
-	const uint32_t y = px / sx, x = px - y * sx;
-	const uint32_t w = x >> 5, bit = x & 31u;
-	const uint64_t wi = zi * plane_words + static_cast<uint64_t>(y) * row_words + w;
-	uint32_t b = planeV[wi];
-	if (w == 0) b |= 1u;
-	// word_base counts the runs that start before this word; bit i set = a run starts at pixel i
-	const uint32_t run = word_base[wi] - 1u + __popc(b & (0xFFFFFFFFu >> (31u - bit)));
-	out[zi * sxy + px] = run_cc[rbase[zi] + run] + static_cast<uint32_t>(comp_off[zi]) + id_base;
-}
-
-// The same with four pixels (16 bytes of ids) per thread: rows whose length is a multiple of four, where the four
-// share a break word.  (4.1 ms -> for 2048 x 2048 x 256: one 4-byte store per lane moved 1 TB/s.)
-__global__ void __launch_bounds__(kBlock) k_paint_components4(
-	const uint32_t* __restrict__ planeV, uint32_t row_words, uint64_t plane_words, uint32_t sx, uint64_t sxy,
-	const uint32_t* __restrict__ word_base, const uint64_t* __restrict__ rbase, const uint32_t* __restrict__ run_cc,
-	const uint64_t* __restrict__ comp_off, uint32_t id_base, uint32_t* __restrict__ out
-) {
-	const uint32_t zi = blockIdx.y;
-	const uint32_t px = (blockIdx.x * kBlock + threadIdx.x) * 4u;
-	if (px >= sxy) return;
-	const uint32_t y = px / sx, x = px - y * sx;
-	const uint32_t w = x >> 5, bit = x & 31u;
-	const uint64_t wi = zi * plane_words + static_cast<uint64_t>(y) * row_words + w;
-	uint32_t b = planeV[wi];
-	if (w == 0) b |= 1u;
-	const uint32_t* cc = run_cc + rbase[zi];
-	const uint32_t add = static_cast<uint32_t>(comp_off[zi]) + id_base;
-	uint32_t run = word_base[wi] - 1u + __popc(b & (0xFFFFFFFFu >> (31u - bit)));
-	uint4 o;
-	o.x = cc[run] + add;
-	run += (b >> (bit + 1u)) & 1u; o.y = cc[run] + add;
-	run += (b >> (bit + 2u)) & 1u; o.z = cc[run] + add;
-	run += (b >> (bit + 3u)) & 1u; o.w = cc[run] + add;
-	*reinterpret_cast<uint4*>(out + zi * sxy + px) = o;
-}
-
-inline void launch_paint_components(hipStream_t s, const uint32_t* planeV, uint32_t row_words, uint64_t plane_words, int64_t sx, int64_t sy, int64_t sz,
-	const uint32_t* word_base, const uint64_t* rbase, const uint32_t* run_cc, const uint64_t* comp_off, uint32_t id_base, uint32_t* out) {
-	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	const bool four = sx % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-	const uint64_t threads = four ? sxy / 4 : sxy;
-	const dim3 grid(static_cast<uint32_t>((threads + kBlock - 1) / kBlock), static_cast<uint32_t>(sz));
-	if (four) hipLaunchKernelGGL(k_paint_components4, grid, dim3(kBlock), 0, s, planeV, row_words, plane_words, static_cast<uint32_t>(sx), sxy, word_base, rbase, run_cc, comp_off, id_base, out);
-	else hipLaunchKernelGGL(k_paint_components, grid, dim3(kBlock), 0, s, planeV, row_words, plane_words, static_cast<uint32_t>(sx), sxy, word_base, rbase, run_cc, comp_off, id_base, out);
-}
-
-// ------------------------------------------------------------------------------
-// label table (labels.hpp:92-152): sorted unique labels and the key of every component.
-// The component -> label list is sorted on device (bitonic network over a power-of-two
-// padded copy), uniqued on the host in one linear pass, and the keys are found by binary
-// search on device and packed at their byte width.
-// ------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_bitonic_step(uint64_t* __restrict__ a, uint32_t j, uint32_t k, uint32_t n) {
-	const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-	if (i >= n) return;
-	const uint32_t l = i ^ j;
-	if (l > i) {
-		const uint64_t x = a[i], y = a[l];
-		const bool up = (i & k) == 0;
-		if ((x > y) == up) { a[i] = y; a[l] = x; }
-	}
-}
-// all steps with j < 2048 of one k-stage inside LDS (2048 elements per workgroup)
-// every stage k = 2 .. 2048 of the network inside blocks of 2048 keys: one launch instead of eleven
-// two steps of the network (distances j and j / 2) in one launch: a thread takes the four elements that the two
-// steps exchange among themselves (the launches of the sort are what it costs: ~6 us each on the label stream)
-__global__ void __launch_bounds__(kBlock) k_bitonic_step2(uint64_t* __restrict__ a, uint32_t j, uint32_t k, uint32_t n) {
-	const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-	if (t >= n / 4u) return;
-	const uint32_t h = j >> 1;
-	const uint32_t lb = static_cast<uint32_t>(__ffs(h)) - 1u;
-	const uint32_t i = (t & (h - 1u)) | ((t >> lb) << (lb + 2u));      // bits h and j clear
-	uint64_t v0 = a[i], v1 = a[i | h], v2 = a[i | j], v3 = a[i | j | h];
-	const bool up = (i & k) == 0;
-	auto cx = [&](uint64_t& x, uint64_t& y) { if ((x > y) == up) { const uint64_t z = x; x = y; y = z; } };
-	cx(v0, v2); cx(v1, v3);
-	cx(v0, v1); cx(v2, v3);
-	a[i] = v0; a[i | h] = v1; a[i | j] = v2; a[i | j | h] = v3;
-}
-
-__global__ void __launch_bounds__(kBlock) k_bitonic_first(uint64_t* __restrict__ a, uint32_t n) {
-	__shared__ uint64_t s[2048];
-	const uint32_t base = blockIdx.x * 2048u;
-	for (uint32_t t = threadIdx.x; t < 2048u; t += kBlock) s[t] = base + t < n ? a[base + t] : ~0ull;
-	__syncthreads();
-	for (uint32_t k = 2; k <= 2048u; k <<= 1) {
-		for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-			for (uint32_t t = threadIdx.x; t < 2048u; t += kBlock) {
-				const uint32_t l = t ^ j;
-				if (l > t) {
-					const uint64_t x = s[t], y = s[l];
-					const bool up = ((base + t) & k) == 0;
-					if ((x > y) == up) { s[t] = y; s[l] = x; }
-				}
-			}
-			__syncthreads();
-		}
-	}
-	for (uint32_t t = threadIdx.x; t < 2048u; t += kBlock) if (base + t < n) a[base + t] = s[t];
-}
-__global__ void __launch_bounds__(kBlock) k_bitonic_local(uint64_t* __restrict__ a, uint32_t j_start, uint32_t k, uint32_t n) {
-	__shared__ uint64_t s[2048];
-	const uint32_t base = blockIdx.x * 2048u;
-	for (uint32_t t = threadIdx.x; t < 2048u; t += kBlock) s[t] = base + t < n ? a[base + t] : ~0ull;
-	__syncthreads();
-	for (uint32_t j = j_start; j > 0; j >>= 1) {
-		for (uint32_t t = threadIdx.x; t < 2048u; t += kBlock) {
-			const uint32_t l = t ^ j;
-			if (l > t) {
-				const uint64_t x = s[t], y = s[l];
-				const bool up = ((base + t) & k) == 0;
-				if ((x > y) == up) { s[t] = y; s[l] = x; }
-			}
-		}
-		__syncthreads();
-	}
-	for (uint32_t t = threadIdx.x; t < 2048u; t += kBlock) if (base + t < n) a[base + t] = s[t];
-}
-__global__ void __launch_bounds__(kBlock) k_pad_copy_u64(const uint64_t* __restrict__ src, uint64_t n, uint64_t* __restrict__ dst, uint64_t n_pad) {
-	const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
-	if (i < n_pad) dst[i] = i < n ? src[i] : ~0ull;
-}
-// sorted[N] -> uniq[U] (first of every run of equal values), U: heads counted per 2048-item
-// block, block counts scanned by one workgroup, heads scattered.
-constexpr uint32_t kUniqPer = 8, kUniqItems = kBlock * kUniqPer;
-__device__ __forceinline__ uint32_t unique_heads(const uint64_t* __restrict__ sorted, uint32_t n, uint32_t i0, uint64_t (&v)[kUniqPer]) {
-	uint32_t flag = 0;
-#pragma unroll
-	for (uint32_t q = 0; q < kUniqPer; q++) {
-		const uint32_t i = i0 + q;
-		v[q] = i < n ? sorted[i] : 0;
-		const uint64_t prev = q ? v[q - 1] : ((i > 0 && i < n) ? sorted[i - 1] : 0);
-		flag |= ((i < n && (i == 0 || v[q] != prev)) ? 1u : 0u) << q;
-	}
-	return flag;
-}
-// grid = ceil(n / 2048)
-__global__ void __launch_bounds__(kBlock) k_unique_count(const uint64_t* __restrict__ sorted, uint32_t n, uint32_t* __restrict__ blk_count) {
-	__shared__ uint32_t s_red[kWaves];
-	uint64_t v[kUniqPer];
-	const uint32_t flag = unique_heads(sorted, n, blockIdx.x * kUniqItems + threadIdx.x * kUniqPer, v);
-	const uint32_t tot = block_sum(static_cast<uint32_t>(__popc(flag)), s_red);
-	if (threadIdx.x == 0) blk_count[blockIdx.x] = tot;
-}
-// one workgroup: exclusive prefix of the block counts (in place) and the total
-__global__ void __launch_bounds__(kBlock) k_unique_scan(uint32_t* __restrict__ blk_count, uint32_t nblk, uint32_t* __restrict__ n_uniq) {
-	__shared__ uint32_t s_scan[kWaves];
-	uint32_t carry = 0;
-	for (uint32_t b0 = 0; b0 < nblk; b0 += kBlock) {
-		const uint32_t b = b0 + threadIdx.x;
-		uint32_t c[1] = { b < nblk ? blk_count[b] : 0u }, tot[1];
-		block_excl_add<1>(c, tot, s_scan);
-		if (b < nblk) blk_count[b] = carry + c[0];
-		carry += tot[0];
-	}
-	if (threadIdx.x == 0) *n_uniq = carry;
-}
-// grid = ceil(n / 2048)
-__global__ void __launch_bounds__(kBlock) k_unique_scatter(const uint64_t* __restrict__ sorted, uint32_t n, const uint32_t* __restrict__ blk_base, uint64_t* __restrict__ uniq) {
-	__shared__ uint32_t s_scan[kWaves];
-	uint64_t v[kUniqPer];
-	const uint32_t flag = unique_heads(sorted, n, blockIdx.x * kUniqItems + threadIdx.x * kUniqPer, v);
-	uint32_t c[1] = { static_cast<uint32_t>(__popc(flag)) }, tot[1];
-	block_excl_add<1>(c, tot, s_scan);
-	uint32_t o = blk_base[blockIdx.x] + c[0];
-#pragma unroll
-	for (uint32_t q = 0; q < kUniqPer; q++) if ((flag >> q) & 1u) uniq[o++] = v[q];
-}
-
-// The component labels are first reduced to their distinct values (a volume has far fewer labels
-// than components: C2 has 1.6 M components and 65 k labels), so that only those are sorted: an
-// open-addressing table keyed by label, then the occupied slots compacted like the unique heads
-// above.  The all-ones label doubles as the empty marker and is noted in a flag of its own.
-constexpr uint64_t kLabelHashEmpty = ~0ull;
-__device__ __forceinline__ uint32_t label_hash(uint64_t v) {
-	v ^= v >> 33; v *= 0xff51afd7ed558ccdull; v ^= v >> 33;
-	return static_cast<uint32_t>(v);
-}
-// grid = ceil(n / 256); table: mask + 1 slots, preset to kLabelHashEmpty
-__global__ void __launch_bounds__(kBlock) k_label_hash_insert(const uint64_t* __restrict__ mapping, uint32_t n, unsigned long long* __restrict__ table, uint32_t mask, uint32_t* __restrict__ has_max) {
-	const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-	if (i >= n) return;
-	const unsigned long long v = mapping[i];
-	if (v == kLabelHashEmpty) { *has_max = 1u; return; }
-	uint32_t h = label_hash(v) & mask;
-	for (uint32_t probe = 0; probe <= mask; probe++) {
-		const unsigned long long seen = table[h];      // most components find their label already there
-		if (seen == v) return;
-		if (seen == kLabelHashEmpty) {
-			const unsigned long long old = atomicCAS(table + h, kLabelHashEmpty, v);
-			if (old == kLabelHashEmpty || old == v) return;
-		}
-		h = (h + 1u) & mask;
-	}
-}
-__device__ __forceinline__ uint32_t hash_occupied(const unsigned long long* __restrict__ table, uint32_t slots, uint32_t i0, uint64_t (&v)[kUniqPer]) {
-	uint32_t flag = 0;
-#pragma unroll
-	for (uint32_t q = 0; q < kUniqPer; q++) {
-		v[q] = i0 + q < slots ? table[i0 + q] : kLabelHashEmpty;
-		flag |= (v[q] != kLabelHashEmpty ? 1u : 0u) << q;
-	}
-	return flag;
-}
-// grid = ceil(slots / 2048)
-__global__ void __launch_bounds__(kBlock) k_label_hash_count(const unsigned long long* __restrict__ table, uint32_t slots, uint32_t* __restrict__ blk_count) {
-	__shared__ uint32_t s_red[kWaves];
-	uint64_t v[kUniqPer];
-	const uint32_t flag = hash_occupied(table, slots, blockIdx.x * kUniqItems + threadIdx.x * kUniqPer, v);
-	const uint32_t tot = block_sum(static_cast<uint32_t>(__popc(flag)), s_red);
-	if (threadIdx.x == 0) blk_count[blockIdx.x] = tot;
-}
-// grid = ceil(slots / 2048); the all-ones label, if seen, goes behind the others
-__global__ void __launch_bounds__(kBlock) k_label_hash_scatter(
-	const unsigned long long* __restrict__ table, uint32_t slots, const uint32_t* __restrict__ blk_base, const uint32_t* __restrict__ n_found,
-	const uint32_t* __restrict__ has_max, uint64_t* __restrict__ out
-) {
-	__shared__ uint32_t s_scan[kWaves];
-	uint64_t v[kUniqPer];
-	const uint32_t flag = hash_occupied(table, slots, blockIdx.x * kUniqItems + threadIdx.x * kUniqPer, v);
-	uint32_t c[1] = { static_cast<uint32_t>(__popc(flag)) }, tot[1];
-	block_excl_add<1>(c, tot, s_scan);
-	uint32_t o = blk_base[blockIdx.x] + c[0];
-#pragma unroll
-	for (uint32_t q = 0; q < kUniqPer; q++) if ((flag >> q) & 1u) out[o++] = v[q];
-	if (blockIdx.x == 0 && threadIdx.x == 0 && *has_max) out[*n_found] = kLabelHashEmpty;
-}
-
-// The flat label section (labels.hpp:123-152) assembled on device:
-//   u64 num_unique | uniq[num_unique] : stored_width | cc_per_slice[sz] : component_width | key[N] : byte_width(num_unique)
-// grid = ceil(max(U, sz, N) / 256) over three index spaces handled by one kernel
-__global__ void __launch_bounds__(kBlock) k_flat_section(
-	const uint64_t* __restrict__ uniq, const uint32_t* __restrict__ n_uniq, int stored_width,
-	const uint32_t* __restrict__ ncomp, uint32_t nslices, int component_width,
-	const uint64_t* __restrict__ mapping, uint32_t n, uint8_t* __restrict__ out, uint32_t* __restrict__ missing
-) {
-	const uint32_t nu = *n_uniq;
-	const int key_width = nu <= 0xFFu ? 1 : (nu <= 0xFFFFu ? 2 : 4);
-	const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-	if (i == 0) for (int b = 0; b < 8; b++) out[b] = static_cast<uint8_t>((static_cast<uint64_t>(nu) >> (8 * b)) & 0xFF);
-	uint8_t* o_uniq = out + 8;
-	uint8_t* o_cc = o_uniq + static_cast<uint64_t>(nu) * stored_width;
-	uint8_t* o_keys = o_cc + static_cast<uint64_t>(nslices) * component_width;
-	if (i < nu) {
-		const uint64_t v = uniq[i];
-		for (int b = 0; b < stored_width; b++) o_uniq[static_cast<uint64_t>(i) * stored_width + b] = static_cast<uint8_t>((v >> (8 * b)) & 0xFF);
-	}
-	if (i < nslices) {
-		const uint32_t v = ncomp[i];
-		for (int b = 0; b < component_width; b++) o_cc[static_cast<uint64_t>(i) * component_width + b] = b < 4 ? static_cast<uint8_t>((v >> (8 * b)) & 0xFF) : 0;
-	}
-	if (i < n) {
-		const uint64_t v = mapping[i];
-		uint32_t lo = 0, hi = nu;          // last index with uniq[idx] <= v
-		while (lo + 1 < hi) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (uniq[mid] <= v) lo = mid; else hi = mid;
-		}
-		if (missing && (nu == 0 || uniq[lo] != v)) *missing = 1u;      // a caller's list (merge_unique) without this label
-		for (int b = 0; b < key_width; b++) o_keys[static_cast<uint64_t>(i) * key_width + b] = static_cast<uint8_t>((lo >> (8 * b)) & 0xFF);
-	}
-}
-
 // one workgroup: final offset of every slice's codes (exclusive prefix of BOC + payload bytes) and
 // what the host needs of them in one buffer: report = [code_len[nslices] | total lo | total hi | errors]
 __global__ void __launch_bounds__(kBlock) k_code_offsets(
@@ -2027,355 +1712,6 @@ CrackResult crack_pass(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, const
 	return result;
 }
 
-struct FlatResult {
-	std::vector<uint32_t> ncomp;      // per slice
-	std::vector<uint32_t> crcs;       // per slice crc32c of the component image
-	uint64_t total = 0;               // components over all slices; mapping stays in e.d_mapping
-};
-
-// geometric-sum table of ckl_runs.hpp (k_run_resolve), cached per slice size
-void ensure_geom_table(ckl_encoder& e, uint64_t sxy) {
-	if (e.g_table_pixels == sxy && e.d_G.p) return;
-	hipStream_t s = e.stream2;
-	const uint32_t npx = static_cast<uint32_t>(sxy);
-	const uint32_t B = 1024, nblk = npx / B + 1;
-	std::vector<uint32_t> g_base(B), blk_g(nblk), blk_x(nblk);
-	const uint32_t X = gf_xpow(32);
-	g_base[0] = 0;
-	for (uint32_t i = 1; i < B; i++) g_base[i] = gf_mul(X, g_base[i - 1] ^ 0x80000000u);
-	const uint32_t gB = gf_mul(X, g_base[B - 1] ^ 0x80000000u);
-	const uint32_t XB = gf_xpow(32ull * B);
-	blk_g[0] = 0; blk_x[0] = 0x80000000u;
-	for (uint32_t k = 1; k < nblk; k++) {
-		blk_g[k] = blk_g[k - 1] ^ gf_mul(blk_x[k - 1], gB);
-		blk_x[k] = gf_mul(blk_x[k - 1], XB);
-	}
-	DevBuf<uint32_t> t_base, t_g, t_x;
-	upload(t_base, g_base, s); upload(t_g, blk_g, s); upload(t_x, blk_x, s);
-	e.d_G.ensure(static_cast<size_t>(npx) + 1);
-	hipLaunchKernelGGL(k_build_geom_table, dim3(npx / kBlock + 1), dim3(kBlock), 0, s, t_base.p, t_g.p, t_x.p, npx, e.d_G.p);
-	CKL_HIP(hipStreamSynchronize(s));
-	e.g_table_pixels = sxy;
-}
-
-// the run kernels' view of the session's run tables (ckl_runs.hpp)
-RunArrays flat_arrays(const ckl_encoder& e) {
-	RunArrays ra;
-	ra.word_base = e.d_word_base.p; ra.rbase = e.d_rbase.p; ra.rcap = e.d_rcap.p;
-	ra.parent = e.d_parent.p; ra.run_start = e.d_run_start.p; ra.run_cc = e.d_run_cc.p;
-	ra.nruns = e.d_nruns.p; ra.ncomp = e.d_ncomp.p; ra.slice_err = e.d_slice_err2.p;
-	ra.comp_pix = e.d_comp_pix.p;
-	return ra;
-}
-
-// component counts, crc accumulators, id widths and error words of the slices lie side by side, the strip kernels' overflow
-// word behind them: flat_collect brings them back in ONE transfer (four separate round trips cost the label path 0.2 ms,
-// and it is what the encode ends with)
-void flat_report_layout(ckl_encoder& e, uint32_t ns, hipStream_t s) {
-	e.d_flat_report.ensure(4 * static_cast<size_t>(ns) + 1);
-	e.d_ncomp.borrow(e.d_flat_report.p, ns); e.d_crc_acc.borrow(e.d_flat_report.p + ns, ns);
-	e.d_idbits.borrow(e.d_flat_report.p + 2 * static_cast<size_t>(ns), ns); e.d_slice_err2.borrow(e.d_flat_report.p + 3 * static_cast<size_t>(ns), ns);
-	CKL_HIP(hipMemsetAsync(e.d_slice_err2.p, 0, (static_cast<size_t>(ns) + 1) * sizeof(uint32_t), s));      // the error words and the overflow word
-}
-
-// the label planes as the run and strip kernels read them
-RunGeom flat_geom(const ckl_encoder& e, int64_t sx, int64_t sy, uint32_t ns) {
-	RunGeom g;
-	g.planeV = plane_v(e); g.planeH = plane_h(e, ns);
-	g.row_words = e.row_words; g.plane_words = e.plane_words;
-	g.flip = 1u;   // a set bit (labels differ) is a break, whatever the stream's crack format
-	g.sx = static_cast<uint32_t>(sx); g.sy = static_cast<uint32_t>(sy);
-	return g;
-}
-
-// encode_flat per-slice part (labels.hpp:56-88) on runs of the label planes, the general pipeline of ckl_runs.hpp:
-// components and their crc32c from one table entry per run.  It serves what the strip kernels below do not take.
-void flat_enqueue_runs(ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz) {
-	hipStream_t s = e.stream2;
-	const uint32_t ns = static_cast<uint32_t>(sz);
-	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	e.flat_strips = false;
-
-	// a run starts at x = 0 of every row and wherever the left neighbour differs
-	// (the host tables stay alive in the session: nothing here waits for the uploads)
-	std::vector<uint64_t>& rbase = e.h_rbase;
-	std::vector<uint32_t>& rcap = e.h_rcap;
-	rbase.assign(ns, 0); rcap.assign(ns, 0);
-	uint64_t rtot = 0;
-	uint32_t max_rcap = 0;
-	for (uint32_t zi = 0; zi < ns; zi++) {
-		const uint64_t runs = static_cast<uint64_t>(sy) + e.count_v[zi];
-		rbase[zi] = rtot; rcap[zi] = static_cast<uint32_t>(runs); rtot += runs;
-		max_rcap = std::max<uint32_t>(max_rcap, static_cast<uint32_t>(runs));
-	}
-	upload(e.d_rbase, rbase, s); upload(e.d_rcap, rcap, s);
-	e.d_word_base.ensure(e.plane_words * ns);
-	e.d_parent.ensure(rtot); e.d_run_start.ensure(rtot); e.d_run_cc.ensure(rtot); e.d_comp_pix.ensure(rtot);
-	e.d_nruns.ensure(ns);
-	flat_report_layout(e, ns, s);
-
-	const RunGeom g = flat_geom(e, sx, sy, ns);
-	const RunArrays ra = flat_arrays(e);
-	hipLaunchKernelGGL(k_run_index, dim3(ns), dim3(kIndexBlock), 0, s, g, ra);
-	launch_run_union(s, ns, g, ra);
-	ResolveScratch rs;
-	rs.nblk = (max_rcap + kBlock - 1) / kBlock;
-	e.d_run_local.ensure(rtot);
-	e.d_blk_roots.ensure(static_cast<size_t>(rs.nblk) * ns);
-	rs.run_local = e.d_run_local.p; rs.blk_roots = e.d_blk_roots.p;
-	launch_run_resolve(s, ns, ra, rs, e.d_G.p, static_cast<uint32_t>(sxy), 0u, e.d_crc_acc.p, e.d_idbits.p);
-	HT_MARK("f:enqueue_runs");
-}
-
-// k_slice_resolve_enc's table: the label stream runs beside two walks per CU and keeps to the 40 KiB that
-// labels_at_walk (encode_typed) leaves it; a slice with more strip components gets a CU's LDS (flat_collect)
-uint32_t flat_resolve_cap(size_t lds_bytes) {
-	uint32_t cap = static_cast<uint32_t>(std::min<size_t>(kResolveCap, (lds_bytes - (kMaxStrips + 64u) * 4u) / 4u));
-	if (const char* env = getenv("CKL_ENC_RESOLVE_CAP")) cap = std::min<uint32_t>(cap, static_cast<uint32_t>(std::max(1, atoi(env))));      // testing: forces the hand-over
-	return cap;
-}
-uint32_t flat_resolve_cap_max(ckl_encoder& e) {
-	if (!e.max_lds) CKL_HIP(hipDeviceGetAttribute(&e.max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
-	return flat_resolve_cap(static_cast<size_t>(e.max_lds) - 8192u);
-}
-
-// Can the strip kernels label this volume, and with what strips?  The host knows every slice's run count: the strips
-// are sized from the densest slice, the decoder's rule (decoder_build) with the true density instead of an estimate
-// and the encoder's table size (kEncStripCap).
-// Not theirs: rows wider than a strip, more strips than the resolve takes, a densest slice of which not one row fits
-// a strip, and a slice that must have more components than the largest resolve table holds (every component has a run
-// that nothing joins to the row above: at least runs minus vertically equal pixel pairs) — noise pays nothing extra.
-bool flat_strip_plan(ckl_encoder& e, int64_t sx, int64_t sy, uint32_t ns) {
-	if (getenv("CKL_ENC_LABEL_RUNS")) return false;      // A/B and tests: the run pipeline for everything
-	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	if (e.row_words == 0 || e.row_words > kStripWords || sxy >= 0xFFFF0000ull) return false;
-	uint64_t runs_max = 0, comps_min = 0;
-	const uint64_t pairs_up = static_cast<uint64_t>(sx) * (sy - 1);
-	for (uint32_t zi = 0; zi < ns; zi++) {
-		const uint64_t runs = static_cast<uint64_t>(sy) + e.count_v[zi];
-		const uint64_t equal_up = pairs_up - std::min<uint64_t>(pairs_up, e.count_h[zi]);
-		runs_max = std::max<uint64_t>(runs_max, runs);
-		comps_min = std::max<uint64_t>(comps_min, runs > equal_up ? runs - equal_up : 0ull);
-	}
-	const double runs_per_row = static_cast<double>(runs_max) / static_cast<double>(sy);
-	const uint32_t fit = static_cast<uint32_t>(0.7 * kEncStripCap / runs_per_row);
-	if (fit < 1u) return false;
-	const uint32_t rows = std::max<uint32_t>(1u, std::min<uint32_t>(kStripWords / e.row_words, fit));
-	const uint32_t nstrips = (static_cast<uint32_t>(sy) + rows - 1) / rows;
-	if (nstrips > kMaxStrips || comps_min > flat_resolve_cap_max(e)) return false;
-	e.flat_strip_rows = rows; e.flat_nstrips = nstrips;
-	e.flat_strip_cap = static_cast<uint32_t>(std::min<uint64_t>(kEncStripCap, static_cast<uint64_t>(rows) * sx));
-	if (const char* env = getenv("CKL_ENC_STRIP_CAP")) e.flat_strip_cap = std::min<uint32_t>(e.flat_strip_cap, static_cast<uint32_t>(std::max(1, atoi(env))));      // testing: strips overflow
-	return true;
-}
-
-StripArrays flat_strip_arrays(const ckl_encoder& e) {
-	StripArrays sa = {};
-	sa.run_lid = e.s_run_lid.p; sa.sc_w = e.s_sc_w.p; sa.sc_cc = e.s_sc_first.p;
-	sa.strip_nruns = e.s_strip_nruns.p; sa.strip_nsc = e.s_strip_nsc.p;
-	sa.seam_first = e.s_seam_first.p; sa.seam_last = e.s_seam_last.p;
-	sa.slice_err = e.d_slice_err2.p; sa.overflow = e.d_flat_report.p + 4 * e.d_ncomp.n;
-	sa.nstrips = e.flat_nstrips; sa.strip_rows = e.flat_strip_rows; sa.cap = e.flat_strip_cap; sa.zbase = 0;
-	return sa;
-}
-
-// k_slice_resolve_enc over all slices with a table of `cap` entries
-void flat_launch_resolve(ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, uint32_t ns, uint32_t cap) {
-	hipStream_t s = e.stream2;
-	e.flat_resolve_cap = cap;
-	e.d_label_slots.ensure(static_cast<size_t>(ns) * cap);
-	ResolveArgs ra = {};
-	ra.cap = cap;
-	EncResolve en;
-	en.labels = labels; en.sxy = static_cast<uint64_t>(sx) * sy; en.slots = e.d_label_slots.p; en.crc_acc = e.d_crc_acc.p; en.idbits = e.d_idbits.p;
-	const RunGeom g = flat_geom(e, sx, sy, ns);
-	const StripArrays sa = flat_strip_arrays(e);
-	const size_t tab_bytes = static_cast<size_t>(cap) * sizeof(uint32_t);
-	if (e.label_src) {
-		// no volume: the slots receive the components' first pixels, flat_collect turns them into labels
-		allow_dynamic_lds(reinterpret_cast<const void*>(&k_slice_resolve_enc_pixels), e.device, tab_bytes);
-		hipLaunchKernelGGL(k_slice_resolve_enc_pixels, dim3(ns), dim3(kResolveBlock), tab_bytes, s, g, sa, ra, en, e.d_ncomp.p);
-		return;
-	}
-	with_label_type(e.dtype_bytes, [&](auto t) {
-		typedef typename decltype(t)::type LABEL;
-		allow_dynamic_lds(reinterpret_cast<const void*>(&k_slice_resolve_enc<LABEL>), e.device, tab_bytes);
-		hipLaunchKernelGGL(k_slice_resolve_enc<LABEL>, dim3(ns), dim3(kResolveBlock), tab_bytes, s, g, sa, ra, en, e.d_ncomp.p);
-	});
-}
-
-// The label stage of a volume (labels.hpp:56-88): the 2-D components of every slice, their count, the crc32c of the
-// component image and the label of every component.  Enqueued on the label stream; the results are collected
-// (flat_collect) while the crack trail runs on the other stream.  Flat labels come from the strip kernels
-// (ckl_strips.hpp): k_strip_ccl_enc labels each strip of rows in LDS, k_slice_resolve_enc joins the strips of a slice —
-// tables per strip component, not per run.  need_runs: the caller reads the run tables afterwards (pins and
-// ckl_encoder_components paint the component volume from run_cc); those and what flat_strip_plan turns down take the
-// run pipeline.
-// beside_walk: the stage starts with the trail's serial walk, which leaves the chip to it.  Only then do the strips take
-// it: in front of the graph kernel (large slices, many nodes) the strip kernel shares the chip with kernels that fill it,
-// and the trail paid for it in full when that was tried at C2; those volumes stay as they were.
-void flat_enqueue(ckl_encoder& e, const void* labels, int64_t sx, int64_t sy, int64_t sz, bool need_runs, bool beside_walk) {
-	hipStream_t s = e.stream2;
-	const uint32_t ns = static_cast<uint32_t>(sz);
-	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	ensure_geom_table(e, sxy);
-	if (need_runs || !beside_walk || !flat_strip_plan(e, sx, sy, ns)) { flat_enqueue_runs(e, sx, sy, sz); return; }
-	e.flat_strips = true;
-	const size_t nst = static_cast<size_t>(e.flat_nstrips) * ns;
-	e.s_strip_nruns.ensure(nst); e.s_strip_nsc.ensure(nst);
-	e.s_seam_first.ensure(nst * e.row_words); e.s_seam_last.ensure(nst * e.row_words);
-	e.s_run_lid.ensure(nst * e.flat_strip_cap); e.s_sc_w.ensure(nst * e.flat_strip_cap); e.s_sc_first.ensure(nst * e.flat_strip_cap);
-	flat_report_layout(e, ns, s);
-	hipLaunchKernelGGL(k_strip_ccl_enc, dim3(e.flat_nstrips, ns), dim3(kBlock), 0, s, flat_geom(e, sx, sy, ns), flat_strip_arrays(e), e.d_G.p, static_cast<uint32_t>(sxy));
-	flat_launch_resolve(e, labels, sx, sy, ns, flat_resolve_cap(kFlatResolveLds));
-	HT_MARK("f:enqueue_strips");
-}
-
-// component counts, crcs, component -> label (labels.hpp:71-88)
-template <typename LABEL>
-void flat_collect(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz, FlatResult& out) {
-	hipStream_t s = e.stream2;
-	const uint32_t ns = static_cast<uint32_t>(sz);
-	const uint64_t sxy = static_cast<uint64_t>(sx) * sy;
-	// laid out by flat_report_layout: ncomp | crc_acc | idbits | slice_err2 | overflow, one transfer
-	const size_t rep_n = 4 * static_cast<size_t>(ns) + 1;
-	std::vector<uint32_t> rep = download(e.d_flat_report.p, rep_n, s);
-	if (e.flat_strips && rep[rep_n - 1] == 2u && e.flat_resolve_cap < flat_resolve_cap_max(e)) {
-		// only k_slice_resolve_enc's table was too small, and it can be larger (over-segmented slices): once more with a
-		// CU's LDS per slice, as the decoder does; the strips' tables stand
-		CKL_HIP(hipMemsetAsync(e.d_flat_report.p + rep_n - 1, 0, sizeof(uint32_t), s));
-		flat_launch_resolve(e, labels, sx, sy, ns, flat_resolve_cap_max(e));
-		HT_MARK("f:resolve_retry");
-		rep = download(e.d_flat_report.p, rep_n, s);
-	}
-	if (e.flat_strips && rep[rep_n - 1]) {
-		// a strip or a resolve table overflowed: the whole volume again on the run pipeline
-		flat_enqueue_runs(e, sx, sy, sz);
-		rep = download(e.d_flat_report.p, rep_n, s);
-	}
-	const uint32_t *acc = rep.data() + ns, *idbits = rep.data() + 2 * static_cast<size_t>(ns), *errs = rep.data() + 3 * static_cast<size_t>(ns);
-	out.ncomp.assign(rep.begin(), rep.begin() + ns);
-	HT_MARK(e.flat_strips ? "f:wait_strips" : "f:wait_runs");
-	for (uint32_t zi = 0; zi < ns; zi++) if (errs[zi]) throw Error(CKL_ERR_RUNTIME, "crackle_amd: run table overflow on z=" + std::to_string(zi));
-	const uint32_t init_term = gf_mul(0xFFFFFFFFu, gf_xpow(32ull * sxy));
-	out.crcs.resize(ns);
-	uint32_t fix_bits = 0xFFFFFFFFu, fix = 0;
-	for (uint32_t zi = 0; zi < ns; zi++) {
-		if (idbits[zi] != fix_bits) { fix_bits = idbits[zi]; fix = gf_xpow(32 - fix_bits); }
-		out.crcs[zi] = ~(gf_mul(acc[zi], fix) ^ init_term);
-	}
-
-	// (the offsets stay alive in the session: nothing here waits for their upload)
-	std::vector<uint64_t>& comp_off = e.h_comp_off;
-	comp_off.assign(ns, 0);
-	uint64_t total = 0;
-	for (uint32_t zi = 0; zi < ns; zi++) { comp_off[zi] = total; total += out.ncomp[zi]; }
-	upload(e.d_comp_off, comp_off, s);
-	e.d_mapping.ensure(total + 1);
-	uint32_t max_ncomp = 1;
-	for (uint32_t zi = 0; zi < ns; zi++) max_ncomp = std::max(max_ncomp, out.ncomp[zi]);
-	const dim3 grid((max_ncomp + kBlock - 1) / kBlock, ns);
-	if (e.label_src) hipLaunchKernelGGL(k_component_labels_from_runs, grid, dim3(kBlock), 0, s, *e.label_src,
-		e.flat_strips ? e.d_label_slots.p : nullptr, e.flat_resolve_cap, e.d_comp_pix.p, e.d_rbase.p, e.d_ncomp.p, e.d_comp_off.p, e.d_mapping.p);
-	else if (e.flat_strips) hipLaunchKernelGGL(k_gather_slots, grid, dim3(kBlock), 0, s, e.d_label_slots.p, e.flat_resolve_cap, e.d_ncomp.p, e.d_comp_off.p, e.d_mapping.p);
-	else hipLaunchKernelGGL(k_mapping_comps<LABEL>, grid, dim3(kBlock), 0, s, labels, flat_arrays(e), sxy, e.d_comp_off.p, e.d_mapping.p);
-	out.total = total;
-}
-
-// The flat label section (labels.hpp:92-152) on device: sort + unique of the component
-// labels, keys by binary search, everything packed at its byte width into e.d_labels_bin.
-// Returns the section size; num_unique comes back for the header arithmetic only.
-uint64_t flat_section(ckl_encoder& e, uint64_t N, int stored_width, int component_width, uint32_t ns, const ckl_encode_overrides* ov = nullptr) {
-	hipStream_t s = e.stream2;
-	if (N > 0x7FFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
-	e.d_n_uniq.ensure(2);
-	e.d_uniq.ensure(N + 1);
-	// the values to sort: the distinct labels when the components are many (a hash pass, then the
-	// sort network runs over tens of thousands instead of millions of keys), else all of them
-	const uint64_t* sort_src = e.d_mapping.p;
-	uint64_t n_sort = N;
-	if (N > 8192 && N <= (1ull << 26) && !getenv("CKL_LABEL_SORT_ALL")) {
-		uint32_t slots = 16384;
-		while (slots < 2 * N) slots <<= 1;
-		e.d_label_hash.ensure(slots);
-		CKL_HIP(hipMemsetAsync(e.d_label_hash.p, 0xFF, static_cast<size_t>(slots) * sizeof(uint64_t), s));
-		CKL_HIP(hipMemsetAsync(e.d_n_uniq.p, 0, 2 * sizeof(uint32_t), s));
-		unsigned long long* table = reinterpret_cast<unsigned long long*>(e.d_label_hash.p);
-		hipLaunchKernelGGL(k_label_hash_insert, dim3(static_cast<uint32_t>((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, e.d_mapping.p, static_cast<uint32_t>(N), table, slots - 1u, e.d_n_uniq.p + 1);
-		const uint32_t hb = (slots + kUniqItems - 1) / kUniqItems;
-		e.d_uniq_blk.ensure(hb + 1);
-		hipLaunchKernelGGL(k_label_hash_count, dim3(hb), dim3(kBlock), 0, s, table, slots, e.d_uniq_blk.p);
-		hipLaunchKernelGGL(k_unique_scan, dim3(1), dim3(kBlock), 0, s, e.d_uniq_blk.p, hb, e.d_n_uniq.p);
-		hipLaunchKernelGGL(k_label_hash_scatter, dim3(hb), dim3(kBlock), 0, s, table, slots, e.d_uniq_blk.p, e.d_n_uniq.p, e.d_n_uniq.p + 1, e.d_uniq.p);
-		const std::vector<uint32_t> found = download(e.d_n_uniq.p, 2, s);
-		n_sort = static_cast<uint64_t>(found[0]) + (found[1] ? 1u : 0u);
-		if (n_sort == 0 || n_sort > N) throw Error(CKL_ERR_RUNTIME, "crackle_amd: label table pass failed");
-		e.d_label_list.ensure(n_sort);
-		CKL_HIP(hipMemcpyAsync(e.d_label_list.p, e.d_uniq.p, n_sort * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-		sort_src = e.d_label_list.p;
-	}
-	// sharded encode: the ranks' lists are merged (and sorted) by the caller anyway, so the slab's distinct
-	// labels go out as the hash pass left them and the local sort is skipped
-	const bool merge_unsorted = ov && ov->merge_unique && sort_src == e.d_label_list.p;
-	uint32_t n_pad = 2048;
-	while (n_pad < n_sort) n_pad <<= 1;
-	if (!merge_unsorted) {
-	e.d_sorted.ensure(n_pad);
-	const uint32_t blocks = (n_pad + kBlock - 1) / kBlock;
-	hipLaunchKernelGGL(k_pad_copy_u64, dim3(blocks), dim3(kBlock), 0, s, sort_src, n_sort, e.d_sorted.p, static_cast<uint64_t>(n_pad));
-	hipLaunchKernelGGL(k_bitonic_first, dim3(n_pad / 2048), dim3(kBlock), 0, s, e.d_sorted.p, n_pad);
-	for (uint32_t k = 4096; k <= n_pad; k <<= 1) {
-		uint32_t j = k >> 1;
-		for (; j >= 4096 && !getenv("CKL_BITONIC_SINGLE_STEPS"); j >>= 2) hipLaunchKernelGGL(k_bitonic_step2, dim3((n_pad / 4 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, e.d_sorted.p, j, k, n_pad);
-		for (; j >= 2048; j >>= 1) hipLaunchKernelGGL(k_bitonic_step, dim3(blocks), dim3(kBlock), 0, s, e.d_sorted.p, j, k, n_pad);
-		hipLaunchKernelGGL(k_bitonic_local, dim3(n_pad / 2048), dim3(kBlock), 0, s, e.d_sorted.p, j, k, n_pad);
-	}
-	{
-		const uint32_t ub = static_cast<uint32_t>((n_sort + kUniqItems - 1) / kUniqItems);
-		e.d_uniq_blk.ensure(ub + 1);
-		hipLaunchKernelGGL(k_unique_count, dim3(ub), dim3(kBlock), 0, s, e.d_sorted.p, static_cast<uint32_t>(n_sort), e.d_uniq_blk.p);
-		hipLaunchKernelGGL(k_unique_scan, dim3(1), dim3(kBlock), 0, s, e.d_uniq_blk.p, ub, e.d_n_uniq.p);
-		hipLaunchKernelGGL(k_unique_scatter, dim3(ub), dim3(kBlock), 0, s, e.d_sorted.p, static_cast<uint32_t>(n_sort), e.d_uniq_blk.p, e.d_uniq.p);
-	}
-	}
-	uint64_t uniq_bound = N;      // entries of the unique list the section kernel may have to write
-	const bool merged_list = ov && ov->merge_unique;
-	if (ov && ov->merge_unique) {
-		// sharded encode: the keys are written against the unique labels of all slabs.  The caller
-		// exchanges the lists now, under the crack trail that is still running on the other stream.
-		HT_MARK("l:enqueue");
-		const uint32_t n_local = merge_unsorted ? static_cast<uint32_t>(n_sort) : download(e.d_n_uniq.p, 1, s)[0];
-		std::vector<uint64_t> local = download(merge_unsorted ? e.d_label_list.p : e.d_uniq.p, n_local, s);      // distinct; sorted unless merge_unsorted
-		HT_MARK("l:local");
-		const uint64_t* merged = nullptr;
-		uint64_t n_merged = 0;
-		if (ov->merge_unique(ov->merge_ctx, local.data(), n_local, &merged, &n_merged) != 0 || (!merged && n_merged))
-			throw Error(CKL_ERR_RUNTIME, "crackle_amd: the merge_unique callback failed");
-		HT_MARK("l:merge");
-		if (n_merged < n_local || n_merged > 0xFFFFFFFFull) throw Error(CKL_ERR_ARG, "crackle_amd: merge_unique returned a list that cannot contain the slab's labels");
-		e.d_uniq.ensure(n_merged + 1);
-		if (n_merged) CKL_HIP(hipMemcpyAsync(e.d_uniq.p, merged, n_merged * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-		const uint32_t nm[2] = { static_cast<uint32_t>(n_merged), 0u };      // the list's length and the section kernel's "label not in the list"
-		CKL_HIP(hipMemcpyAsync(e.d_n_uniq.p, nm, sizeof(nm), hipMemcpyHostToDevice, s));
-		CKL_HIP(hipStreamSynchronize(s));      // `nm` and the caller's list may go away
-		e.d_labels_bin.ensure(8 + n_merged * static_cast<uint64_t>(stored_width) + static_cast<uint64_t>(ns) * component_width + N * 4 + 16);
-		uniq_bound = std::max<uint64_t>(uniq_bound, n_merged);
-	}
-	// worst case: every component has its own label and 4-byte keys
-	e.d_labels_bin.ensure(8 + N * static_cast<uint64_t>(stored_width) + static_cast<uint64_t>(ns) * component_width + N * 4 + 16);
-	const uint64_t work = std::max<uint64_t>(std::max<uint64_t>(uniq_bound, ns), 1);
-	hipLaunchKernelGGL(k_flat_section, dim3(static_cast<uint32_t>((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-		e.d_uniq.p, e.d_n_uniq.p, stored_width, e.d_ncomp.p, ns, component_width, e.d_mapping.p, static_cast<uint32_t>(N), e.d_labels_bin.p,
-		merged_list ? e.d_n_uniq.p + 1 : nullptr);
-	HT_MARK("l:enqueue");
-	const std::vector<uint32_t> report = download(e.d_n_uniq.p, merged_list ? 2 : 1, s);
-	const uint32_t nu = report[0];
-	HT_MARK("l:wait");
-	// the length alone does not show it: keys against a list without one of the slab's labels (or one that is not sorted) would name its neighbour
-	if (merged_list && report[1]) throw Error(CKL_ERR_ARG, "crackle_amd: merge_unique returned a list that lacks a label of the slab");
-	return 8 + static_cast<uint64_t>(nu) * stored_width + static_cast<uint64_t>(ns) * component_width + N * static_cast<uint64_t>(byte_width(nu));
-}
-
 }  // namespace
 
 // The stream's header as the volume's statistics decide it (crackle.hpp:50-64, 233-235) unless the overrides do;
@@ -2439,6 +1775,196 @@ struct EncodeRequest {
 	const ckl_encode_overrides* overrides = nullptr;
 };
 
+// When does the label stream's component labelling run?  Beside the trail's chip-filling kernels the two
+// take turns (graph 0.2 -> 0.65 ms at C2); the serial walk leaves the chip idle for a millisecond, and
+// two walks per CU leave room for other workgroups when they keep to a third of the LDS each.  Then the
+// label stream starts with the walk (it waits for the event in front of it): AT_WALK.  Otherwise it starts
+// in front of the graph kernel, BEFORE_GRAPH: slices too large for that (decided from their size, before the node
+// counts are known), CKL_NO_OVERLAP, CKL_LABELS_AT_WALK=0; or behind it, AFTER_GRAPH, when the node counts say that the
+// walks leave no room.  (The sharded encode's label stream also carries the ranks' exchange of unique
+// labels: 0.5 ms on the host.  It fits since the slab's labels are exchanged unsorted.)
+enum class LabelStart { BEFORE_GRAPH, AFTER_GRAPH, AT_WALK };
+
+// The one place that decides it.  Asked twice: before the planes pass, without the graph's node counts, the answer is
+// BEFORE_GRAPH or "not before" (AFTER_GRAPH); with them (e.count_special of graph_pass) it is final.
+LabelStart label_start(const ckl_encoder& e, int64_t sx, int64_t sy, bool no_overlap, const std::vector<uint32_t>* count_special = nullptr) {
+	const char* at_walk = getenv("CKL_LABELS_AT_WALK");
+	if (no_overlap || static_cast<uint64_t>(sx) * sy > (1536ull * 1536ull) || (at_walk && atoi(at_walk) == 0)) return LabelStart::BEFORE_GRAPH;
+	if (!count_special) return LabelStart::AFTER_GRAPH;
+	uint32_t max_special = 0;
+	for (uint32_t v : *count_special) max_special = std::max(max_special, v);
+	int max_lds = 0;
+	CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
+	const bool beside_walks = max_special < 5000 && 2 * trail_walk_lds(max_special) + kFlatResolveLds <= static_cast<size_t>(max_lds);
+	return beside_walks ? LabelStart::AT_WALK : LabelStart::AFTER_GRAPH;
+}
+
+// What the early output buffer (label_stage) allows for behind the label section: the stored model and the
+// crack code bytes, estimated from the edge and node counts: every edge is one code, a branch
+// costs a few more; 2 bits per code (markov: at most 3), BOC index of a few chains per slice
+uint64_t estimate_code_bytes(const ckl_encoder& e, int64_t sx, int64_t sy, int64_t sz, bool permissible, int markov_order) {
+	uint64_t est_code_bytes = 0;
+	const int xw = byte_width(static_cast<uint64_t>(sx) + 1), yw = byte_width(static_cast<uint64_t>(sy) + 1);
+	for (int64_t z = 0; z < sz; z++) {
+		const uint64_t codes = crack_edges(e, sx, sy, z, permissible) + 4ull * (static_cast<uint64_t>(e.count_special[z]) + e.count_corner[z]) + 16;
+		est_code_bytes += (markov_order ? (3 * codes + 7) / 8 : (codes + 3) / 4) + 8;
+		est_code_bytes += 4 + yw + 64ull * (yw + 2 * xw);
+	}
+	if (getenv("CKL_SMALL_ESTIMATE")) est_code_bytes = 0;      // testing: the stream outgrows the early buffer
+	const uint64_t model_bytes_est = markov_order ? (1ull << (2 * markov_order)) : 0;
+	return model_bytes_est + est_code_bytes;
+}
+
+// where the label section begins: behind the header and the z-index
+inline uint64_t labels_offset(const Header& head) { return head.header_bytes() + head.grid_index_bytes(); }
+
+// what the label side of a run leaves for the assembly
+struct LabelSide {
+	FlatResult flat;                       // per slice: the components and the crc of the component image
+	uint64_t label_bytes = 0;
+	std::vector<uint8_t> pins_binary;      // pin label section (host built)
+	uint32_t labels_crc = 0;               // of the flat label section, unless labels_stay
+	bool labels_stay = false;              // the label section and its crc stay on the device until the background copy
+	HostOut<uint8_t> early;                // flat labels: the output buffer, taken early, with the label section in it unless labels_stay
+	uint64_t early_cap = 0;
+};
+
+// The label side (labels.hpp:30-155): runs on the host while the trail kernels execute (CrackRequest::overlap).  The
+// components + crcs that were started on the label stream are collected here, or started here when they start with the
+// walk; then the label section.  behind_labels: estimate_code_bytes.
+template <typename LABEL>
+LabelSide label_stage(
+	ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz, const Header& head, const EncodeRequest& req, LabelStart start, uint64_t behind_labels
+) {
+	LabelSide r;
+	hipStream_t s2 = e.stream2;
+	if (start == LabelStart::AT_WALK) {
+		CKL_HIP(hipStreamWaitEvent(s2, e.evd0, 0));      // (starting one kernel earlier, beside k_trail_components, cost 0.2 ms)
+		flat_enqueue(e, labels, sx, sy, sz, head.label_format != FLAT, true);
+	}
+	flat_collect(e, labels, static_cast<int>(sizeof(LABEL)), sx, sy, sz, r.flat);
+	HT_MARK("flat");
+	const uint64_t N = r.flat.total;
+	if (head.label_format == PINS_VARIABLE_WIDTH) {
+		// pins (pins.hpp:348-403, labels.hpp:157-344): components and crcs come from the
+		// device passes above; the order-sensitive cover runs on the host (ckl_pins.hip)
+		if (N > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
+		e.d_cc_volume.ensure(static_cast<uint64_t>(sx) * sy * sz);
+		paint_components(e, sx, sy, sz, 0u, e.d_cc_volume.p);
+		r.pins_binary = pins_section_plain<LABEL>(e, labels, e.d_cc_volume.p, e.d_mapping.p, sx, sy, sz, N, r.flat.ncomp, head.pin_index_width(), head.stored_data_width, req.auto_bgcolor, req.manual_bgcolor);
+		r.label_bytes = r.pins_binary.size();
+		return r;
+	}
+	const uint64_t off_labels = labels_offset(head);
+	r.label_bytes = flat_section(e, N, head.stored_data_width, byte_width(static_cast<uint64_t>(sx) * sy), static_cast<uint32_t>(sz), req.overrides);
+	HT_MARK("label_table");
+	r.labels_stay = e.async_host_copy && e.keep_device_stream && !e.defer_codes && r.label_bytes > 0;
+	// The output buffer is taken now, sized with an estimate of the crack code bytes, so that
+	// the label section is copied out and checksummed while the trail still runs; a stream
+	// that outgrows the estimate is moved to a larger buffer at assembly.
+	r.early_cap = off_labels + r.label_bytes + behind_labels + 4ull * (sz + 1) + 64;
+	r.early = host_out<uint8_t>(r.early_cap);
+	HT_MARK("l:buffer");
+	uint8_t* eo = r.early.get();
+	// (one copy: four pieces with an event each, checksummed while the next was on the link, saved 0.04 ms
+	// and now and then stalled the enqueueing thread for milliseconds)
+	if (r.labels_stay) {
+		// the caller goes on from the stream in HBM: the section's crc32c is taken on the device and the section itself travels
+		// to the host with the crack codes, in the background (until round 5 both sat on the encode's tail: 8 MB over the link,
+		// then the host's crc over them, 0.25 ms at C2)
+		e.d_labels_crc.ensure(1 + kBlock);
+		if (!e.ev_labels_crc) CKL_HIP(hipEventCreateWithFlags(&e.ev_labels_crc, hipEventDisableTiming));
+		crc32c_device(e.d_labels_bin.p, r.label_bytes, e.d_labels_crc.p + 1, e.d_labels_crc.p, s2);
+		CKL_HIP(hipEventRecord(e.ev_labels_crc, s2));
+	}
+	else {
+		if (r.label_bytes) CKL_HIP(hipMemcpyAsync(eo + off_labels, e.d_labels_bin.p, r.label_bytes, hipMemcpyDeviceToHost, s2));
+		CKL_HIP(hipStreamSynchronize(s2));
+		r.labels_crc = crc32c(eo + off_labels, r.label_bytes);
+	}
+	HT_MARK("labels_d2h");
+	return r;
+}
+
+// Where a stream's sections lie (crackle.hpp:171-216):
+//   header | z-index + crc | labels | model | crack codes | labels crc | slice crcs
+// A version 0 stream, which only reencode_markov writes, has a 24-byte header, no crc behind the z-index and no tail.
+struct StreamLayout { uint64_t off_index, off_labels, off_model, off_codes, off_tail, total; };
+StreamLayout stream_layout(const Header& head, uint64_t model_bytes, uint64_t code_bytes) {
+	StreamLayout l;
+	l.off_index = head.header_bytes();
+	l.off_labels = labels_offset(head);
+	l.off_model = l.off_labels + head.num_label_bytes;
+	l.off_codes = l.off_model + model_bytes;
+	l.off_tail = l.off_codes + code_bytes;
+	l.total = l.off_tail + (head.format_version == 0 ? 0 : 4ull * (static_cast<uint64_t>(head.sz) + 1));
+	return l;
+}
+
+inline void put4(uint8_t* p, uint32_t v) { for (int b = 0; b < 4; b++) p[b] = static_cast<uint8_t>((v >> (8 * b)) & 0xFF); }
+
+// what frames the sections that are copied or computed elsewhere: the header, the z-index (every slice's code bytes) with its
+// crc, and the stored model
+void write_frame(uint8_t* o, const Header& head, const StreamLayout& l, const std::vector<uint32_t>& code_len, const std::vector<uint8_t>& stored_model) {
+	std::vector<uint8_t> hb;
+	head.write(hb);
+	memcpy(o, hb.data(), hb.size());
+	const uint64_t sz = head.sz;
+	for (uint64_t z = 0; z < sz; z++) put4(o + l.off_index + 4 * z, code_len[z]);
+	if (head.format_version != 0) put4(o + l.off_index + 4 * sz, crc32c(o + l.off_index, 4 * sz));
+	if (!stored_model.empty()) memcpy(o + l.off_model, stored_model.data(), stored_model.size());
+}
+
+// The bulky sections reach the stream `o`, whose frame, flat label section (unless labels_stay) and tail the host has
+// written: the stream once more in HBM if the session keeps one, then the crack codes' way to the host.
+void assemble(ckl_encoder& e, uint8_t* o, const Header& head, const StreamLayout& l, bool labels_stay) {
+	hipStream_t s = e.stream;
+	const uint64_t label_bytes = head.num_label_bytes, model_bytes = l.off_codes - l.off_model, code_bytes = l.off_tail - l.off_codes;
+	e.device_stream_bytes = 0;
+	if (e.keep_device_stream) {
+		// the same bytes once more in HBM, for a decoder that takes its stream from the device
+		// (ckl_decoder_create_device): the two bulky sections are device-to-device copies, the small
+		// ones go up from the host buffer
+		e.d_stream_out.ensure(l.total + 16);
+		uint8_t* ds = e.d_stream_out.p;
+		const void* up = head.label_format == FLAT ? o : nullptr;      // (by kernel for flat label streams only, see upload_small; o: a pinned, device-mapped block when the stream is 64 KiB or more)
+		upload_small(ds, o, l.off_labels, s, up);
+		if (label_bytes) {
+			if (head.label_format == FLAT) copy_bytes_device(e.d_labels_bin.p, ds + l.off_labels, label_bytes, s);
+			else CKL_HIP(hipMemcpyAsync(ds + l.off_labels, o + l.off_labels, label_bytes, hipMemcpyHostToDevice, s));
+		}
+		if (model_bytes) upload_small(ds + l.off_model, o + l.off_model, model_bytes, s, up);
+		if (code_bytes) copy_bytes_device(e.d_codes_out.p, ds + l.off_codes, code_bytes, s);
+		upload_small(ds + l.off_tail, o + l.off_tail, l.total - l.off_tail, s, up);
+		if (labels_stay) {
+			CKL_HIP(hipStreamWaitEvent(s, e.ev_labels_crc, 0));
+			CKL_HIP(hipMemcpyAsync(ds + l.off_tail, e.d_labels_crc.p, 4, hipMemcpyDeviceToDevice, s));
+		}
+		e.device_stream_bytes = l.total;
+	}
+	// the crack codes' copy to the host goes LAST: started first, its 13 MB kept the link busy and the 2 KB header
+	// upload above waited 0.19 ms behind it (rocprofv3 timeline, round 4)
+	if (code_bytes && !e.defer_codes) {
+		if (e.async_host_copy && e.keep_device_stream) {
+			// the caller goes on with the stream in HBM (a decoder, the next volume's planes) while the codes
+			// cross PCIe: ckl_encoder_host_wait before the host bytes are read
+			if (!e.stream_copy) CKL_HIP(hipStreamCreateWithFlags(&e.stream_copy, hipStreamNonBlocking));
+			if (!e.ev_codes) CKL_HIP(hipEventCreateWithFlags(&e.ev_codes, hipEventDisableTiming));
+			CKL_HIP(hipEventRecord(e.ev_codes, s));
+			CKL_HIP(hipStreamWaitEvent(e.stream_copy, e.ev_codes, 0));
+			CKL_HIP(hipMemcpyAsync(o + l.off_codes, e.d_codes_out.p, code_bytes, hipMemcpyDeviceToHost, e.stream_copy));
+			if (labels_stay) {
+				CKL_HIP(hipMemcpyAsync(o + l.off_labels, e.d_labels_bin.p, label_bytes, hipMemcpyDeviceToHost, e.stream_copy));
+				CKL_HIP(hipMemcpyAsync(o + l.off_tail, e.d_labels_crc.p, 4, hipMemcpyDeviceToHost, e.stream_copy));
+			}
+			e.host_copy_pending = true;
+		}
+		else CKL_HIP(hipMemcpyAsync(o + l.off_codes, e.d_codes_out.p, code_bytes, hipMemcpyDeviceToHost, s));
+	}
+}
+
+// One run, in the order of its steps (DESIGN.md §8 states the schedule): planes, graph, the label stream's start at one of
+// three places (label_start), the crack trail with the label side under it, the frame, the assembly.
 template <typename LABEL>
 void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, int64_t sz, const EncodeRequest& req, uint8_t** out, uint64_t* out_len) {
 	const ckl_encode_overrides* const ov = req.overrides;
@@ -2454,10 +1980,10 @@ void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	const bool have_planes = voxels > 0 && (e.label_src ? planes_cached(e, e.label_src, sx, sy, sz) : ov && planes_cached(e, labels, sx, sy, sz));
 	e.planes_for = nullptr;       // single use: the caller may change the volume afterwards
 	if (e.label_src && voxels > 0 && !have_planes) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: recompress without its planes");
-	const bool labels_first = getenv("CKL_NO_OVERLAP") || static_cast<uint64_t>(sx) * sy > (1536ull * 1536ull)
-		|| (getenv("CKL_LABELS_AT_WALK") && atoi(getenv("CKL_LABELS_AT_WALK")) == 0);
+	const bool no_overlap = getenv("CKL_NO_OVERLAP") != nullptr;      // diagnostic: kernel timings without the two streams competing
+	LabelStart start = label_start(e, sx, sy, no_overlap);
 	// (a label stream that starts in front of the graph kernel sizes its run arrays from the planes' counts: no deferral then)
-	if (voxels > 0 && !have_planes) planes_pass<LABEL>(e, labels, sx, sy, sz, &st, !labels_first);
+	if (voxels > 0 && !have_planes) planes_pass<LABEL>(e, labels, sx, sy, sz, &st, start != LabelStart::BEFORE_GRAPH);
 	else if (have_planes) st = e.planes_stats;      // overrides that force nothing still decide from the volume
 	ht.mark("planes");
 	bool graph_done = false;
@@ -2470,39 +1996,24 @@ void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 		ht.mark("graph");
 	}
 	Header head = stream_header(static_cast<int>(sizeof(LABEL)), sx, sy, sz, st, req.allow_pins, req.fortran_order, req.markov_model_order, ov);
-	const int stored_width = head.stored_data_width;
 	e.uploads_by_kernel = head.label_format == FLAT;
 	if (voxels == 0) { hand_out(header_bytes(head), OutAlloc::MALLOC, out, out_len); return; }
 	if (req.optimize_pins) throw Error(CKL_ERR_ARG, "crackle_amd: allow_pins=2 (find_optimal_pins) is out of scope");
 	if (head.label_format != FLAT && head.label_format != PINS_VARIABLE_WIDTH) throw Error(CKL_ERR_ARG, "crackle_amd: unsupported label format");
 	if (head.markov_model_order > 13) throw Error(CKL_ERR_ARG, "crackle_amd: markov_model_order > 13 is not supported on device");
 
-	// labels (labels.hpp:30-155): components + crcs start on the label stream now and are
-	// collected while the crack trail runs
-	// When does the label stream's component labelling run?  Beside the trail's chip-filling kernels the two
-	// take turns (graph 0.2 -> 0.65 ms at C2); the serial walk leaves the chip idle for a millisecond, and
-	// two walks per CU leave room for other workgroups when they keep to a third of the LDS each.  Then the
-	// label stream starts with the walk (it waits for the event in front of it).  Otherwise it starts now,
-	// in front of the graph kernel: slices too large for that (decided from their size, before the node
-	// counts are known).  (The sharded encode's label stream also carries the ranks' exchange of unique
-	// labels: 0.5 ms on the host.  It fits since the slab's labels are exchanged unsorted.)
-	bool labels_at_walk = false;
+	// labels (labels.hpp:30-155): components + crcs start on the label stream, here, behind the graph kernel or with
+	// the walk (label_stage), and are collected while the crack trail runs
 	const bool need_runs = head.label_format != FLAT;      // pins paint the component volume from the run tables
-	if (labels_first && !graph_done) flat_enqueue(e, labels, sx, sy, sz, need_runs, false);
+	if (start == LabelStart::BEFORE_GRAPH) flat_enqueue(e, labels, sx, sy, sz, need_runs, false);
 	const bool trail_cached = !graph_done && have_planes && ov && ov->has_model && head.markov_model_order > 0 && e.trail_for == static_cast<const void*>(labels)
 		&& e.trail_perm == (head.crack_format == PERMISSIBLE) && e.trail_order == head.markov_model_order;
 	e.trail_for = nullptr;
 	if (graph_done && e.graph_permissible != (head.crack_format == PERMISSIBLE)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: internal: device and host disagree on the crack format");
 	if (!trail_cached && !graph_done) graph_pass(e, sx, sy, sz, graph_format(head.crack_format == PERMISSIBLE));
 	ht.mark("graph");
-	if (!labels_first) {
-		uint32_t max_special = 0;
-		for (uint32_t v : e.count_special) max_special = std::max(max_special, v);
-		int max_lds = 0;
-		CKL_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e.device));
-		labels_at_walk = max_special < 5000 && 2 * trail_walk_lds(max_special) + kFlatResolveLds <= static_cast<size_t>(max_lds);
-		if (!labels_at_walk) flat_enqueue(e, labels, sx, sy, sz, need_runs, false);
-	}
+	start = label_start(e, sx, sy, no_overlap, &e.count_special);
+	if (start == LabelStart::AFTER_GRAPH) flat_enqueue(e, labels, sx, sy, sz, need_runs, false);
 
 	const bool permissible = head.crack_format == PERMISSIBLE;
 	// if no slice has a crack edge the reference resets the markov order to 0 (crackle.hpp:107-118)
@@ -2522,79 +2033,9 @@ void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 		crq.model = &forced_model;
 	}
 
-	FlatResult fr;
-	std::vector<uint8_t> pins_binary;      // pin label section (host built)
-	uint64_t label_bytes = 0;
-	const uint64_t off_index = Header::kBytes;
-	const uint64_t off_labels = off_index + 4ull * (sz + 1);
-	// crack code bytes, estimated from the edge and node counts: every edge is one code, a branch
-	// costs a few more; 2 bits per code (markov: at most 3), BOC index of a few chains per slice
-	uint64_t est_code_bytes = 0;
-	{
-		const int xw = byte_width(static_cast<uint64_t>(sx) + 1), yw = byte_width(static_cast<uint64_t>(sy) + 1);
-		for (int64_t z = 0; z < sz; z++) {
-			const uint64_t codes = crack_edges(e, sx, sy, z, permissible) + 4ull * (static_cast<uint64_t>(e.count_special[z]) + e.count_corner[z]) + 16;
-			est_code_bytes += (head.markov_model_order ? (3 * codes + 7) / 8 : (codes + 3) / 4) + 8;
-			est_code_bytes += 4 + yw + 64ull * (yw + 2 * xw);
-		}
-	}
-	if (getenv("CKL_SMALL_ESTIMATE")) est_code_bytes = 0;      // testing: the stream outgrows the early buffer
-	const uint64_t model_bytes_est = head.markov_model_order ? (1ull << (2 * head.markov_model_order)) : 0;
-	struct HostOut { void* p = nullptr; ~HostOut() { if (p) host_out_free(p); } } early;
-	uint64_t early_cap = 0;
-	uint32_t labels_crc = 0;
-	const int component_width = byte_width(static_cast<uint64_t>(sx) * sy);
-	hipStream_t s2 = e.stream2;
-	bool labels_stay = false;      // set by label_side: the label section and its crc stay on the device until the background copy
-	auto label_side = [&]() {
-		if (labels_at_walk) {
-			CKL_HIP(hipStreamWaitEvent(s2, e.evd0, 0));      // (starting one kernel earlier, beside k_trail_components, cost 0.2 ms)
-			flat_enqueue(e, labels, sx, sy, sz, need_runs, true);
-		}
-		flat_collect<LABEL>(e, labels, sx, sy, sz, fr);
-		HT_MARK("flat");
-		const uint64_t N = fr.total;
-		if (head.label_format == PINS_VARIABLE_WIDTH) {
-			// pins (pins.hpp:348-403, labels.hpp:157-344): components and crcs come from the
-			// device passes above; the order-sensitive cover runs on the host (ckl_pins.hip)
-			if (N > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
-			e.d_cc_volume.ensure(voxels);
-			launch_paint_components(s2, plane_v(e), e.row_words, e.plane_words, sx, sy, sz, e.d_word_base.p, e.d_rbase.p, e.d_run_cc.p, e.d_comp_off.p, 0u, e.d_cc_volume.p);
-			pins_binary = pins_section_plain<LABEL>(e, labels, e.d_cc_volume.p, e.d_mapping.p, sx, sy, sz, N, fr.ncomp, head.pin_index_width(), stored_width, req.auto_bgcolor, req.manual_bgcolor);
-			label_bytes = pins_binary.size();
-		}
-		else {
-			label_bytes = flat_section(e, N, stored_width, component_width, static_cast<uint32_t>(sz), ov);
-			HT_MARK("label_table");
-			labels_stay = e.async_host_copy && e.keep_device_stream && !e.defer_codes && label_bytes > 0;
-			// The output buffer is taken now, sized with an estimate of the crack code bytes, so that
-			// the label section is copied out and checksummed while the trail still runs; a stream
-			// that outgrows the estimate is moved to a larger buffer at assembly.
-			early_cap = off_labels + label_bytes + model_bytes_est + est_code_bytes + 4ull * (sz + 1) + 64;
-			early.p = host_out_alloc(early_cap);
-			HT_MARK("l:buffer");
-			uint8_t* eo = static_cast<uint8_t*>(early.p);
-			// (one copy: four pieces with an event each, checksummed while the next was on the link, saved 0.04 ms
-			// and now and then stalled the enqueueing thread for milliseconds)
-			if (labels_stay) {
-				// the caller goes on from the stream in HBM: the section's crc32c is taken on the device and the section itself travels
-				// to the host with the crack codes, in the background (until round 5 both sat on the encode's tail: 8 MB over the link,
-				// then the host's crc over them, 0.25 ms at C2)
-				e.d_labels_crc.ensure(1 + kBlock);
-				if (!e.ev_labels_crc) CKL_HIP(hipEventCreateWithFlags(&e.ev_labels_crc, hipEventDisableTiming));
-				crc32c_device(e.d_labels_bin.p, label_bytes, e.d_labels_crc.p + 1, e.d_labels_crc.p, s2);
-				CKL_HIP(hipEventRecord(e.ev_labels_crc, s2));
-			}
-			else {
-				if (label_bytes) CKL_HIP(hipMemcpyAsync(eo + off_labels, e.d_labels_bin.p, label_bytes, hipMemcpyDeviceToHost, s2));
-				CKL_HIP(hipStreamSynchronize(s2));
-				labels_crc = crc32c(eo + off_labels, label_bytes);
-			}
-			HT_MARK("labels_d2h");
-		}
-	};
-
-	const bool no_overlap = getenv("CKL_NO_OVERLAP") != nullptr;      // diagnostic: kernel timings without the two streams competing
+	const uint64_t behind_labels = estimate_code_bytes(e, sx, sy, sz, permissible, head.markov_model_order);
+	LabelSide side;
+	auto label_side = [&]() { side = label_stage<LABEL>(e, labels, sx, sy, sz, head, req, start, behind_labels); };
 	if (!no_overlap) crq.overlap = label_side;
 	const CrackResult cr = crack_pass(e, sx, sy, sz, crq);
 	if (no_overlap) label_side();
@@ -2602,75 +2043,25 @@ void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	std::vector<uint8_t> stored_model;
 	if (head.markov_model_order > 0) stored_model = markov_model_to_stored(cr.model);
 
-	// assembly (crackle.hpp:171-216), straight into the caller's buffer:
-	// header | z-index + crc | labels | model | crack codes | labels crc | slice crcs
-	head.num_label_bytes = label_bytes;
-	const uint64_t off_model = off_labels + label_bytes;
-	const uint64_t off_codes = off_model + stored_model.size();
-	const uint64_t off_tail = off_codes + cr.total;
-	const uint64_t total = off_tail + 4ull * (sz + 1);
+	// assembly (crackle.hpp:171-216), straight into the caller's buffer
+	head.num_label_bytes = side.label_bytes;
+	const StreamLayout l = stream_layout(head, stored_model.size(), cr.total);
 	uint8_t* o;
-	if (early.p && total <= early_cap) { o = static_cast<uint8_t*>(early.p); early.p = nullptr; }
+	if (side.early && l.total <= side.early_cap) o = side.early.release();
 	else {
-		o = static_cast<uint8_t*>(host_out_alloc(total));
-		if (early.p && label_bytes) memcpy(o + off_labels, static_cast<uint8_t*>(early.p) + off_labels, label_bytes);
+		o = static_cast<uint8_t*>(host_out_alloc(l.total));
+		if (side.early && side.label_bytes) memcpy(o + l.off_labels, side.early.get() + l.off_labels, side.label_bytes);
 	}
 	try {
 		e.last_codes_total = cr.total;
 		if (head.label_format == PINS_VARIABLE_WIDTH) {
-			if (label_bytes) memcpy(o + off_labels, pins_binary.data(), label_bytes);
-			labels_crc = crc32c(o + off_labels, label_bytes);
+			if (side.label_bytes) memcpy(o + l.off_labels, side.pins_binary.data(), side.label_bytes);
+			side.labels_crc = crc32c(o + l.off_labels, side.label_bytes);
 		}
-		std::vector<uint8_t> hb;
-		head.write(hb);
-		memcpy(o, hb.data(), hb.size());
-		auto put4 = [&](uint64_t at, uint32_t v) { for (int b = 0; b < 4; b++) o[at + b] = static_cast<uint8_t>((v >> (8 * b)) & 0xFF); };
-		for (int64_t z = 0; z < sz; z++) put4(off_index + 4ull * z, cr.code_len[z]);
-		put4(off_index + 4ull * sz, crc32c(o + off_index, 4ull * sz));
-		if (!stored_model.empty()) memcpy(o + off_model, stored_model.data(), stored_model.size());
-		for (int64_t z = 0; z < sz; z++) put4(off_tail + 4 + 4ull * z, fr.crcs[z]);
-		put4(off_tail, labels_crc);
-		e.device_stream_bytes = 0;
-		if (e.keep_device_stream) {
-			// the same bytes once more in HBM, for a decoder that takes its stream from the device
-			// (ckl_decoder_create_device): the two bulky sections are device-to-device copies, the small
-			// ones go up from the host buffer
-			e.d_stream_out.ensure(total + 16);
-			uint8_t* ds = e.d_stream_out.p;
-			const void* up = head.label_format == FLAT ? o : nullptr;      // (by kernel for flat label streams only, see upload_small; o: a pinned, device-mapped block when the stream is 64 KiB or more)
-			upload_small(ds, o, off_labels, s, up);
-			if (label_bytes) {
-				if (head.label_format == FLAT) copy_bytes_device(e.d_labels_bin.p, ds + off_labels, label_bytes, s);
-				else CKL_HIP(hipMemcpyAsync(ds + off_labels, o + off_labels, label_bytes, hipMemcpyHostToDevice, s));
-			}
-			if (!stored_model.empty()) upload_small(ds + off_model, o + off_model, stored_model.size(), s, up);
-			if (cr.total) copy_bytes_device(e.d_codes_out.p, ds + off_codes, cr.total, s);
-			upload_small(ds + off_tail, o + off_tail, 4ull * (sz + 1), s, up);
-			if (labels_stay) {
-				CKL_HIP(hipStreamWaitEvent(s, e.ev_labels_crc, 0));
-				CKL_HIP(hipMemcpyAsync(ds + off_tail, e.d_labels_crc.p, 4, hipMemcpyDeviceToDevice, s));
-			}
-			e.device_stream_bytes = total;
-		}
-		// the crack codes' copy to the host goes LAST: started first, its 13 MB kept the link busy and the 2 KB header
-		// upload above waited 0.19 ms behind it (rocprofv3 timeline, round 4)
-		if (cr.total && !e.defer_codes) {
-			if (e.async_host_copy && e.keep_device_stream) {
-				// the caller goes on with the stream in HBM (a decoder, the next volume's planes) while the codes
-				// cross PCIe: ckl_encoder_host_wait before the host bytes are read
-				if (!e.stream_copy) CKL_HIP(hipStreamCreateWithFlags(&e.stream_copy, hipStreamNonBlocking));
-				if (!e.ev_codes) CKL_HIP(hipEventCreateWithFlags(&e.ev_codes, hipEventDisableTiming));
-				CKL_HIP(hipEventRecord(e.ev_codes, s));
-				CKL_HIP(hipStreamWaitEvent(e.stream_copy, e.ev_codes, 0));
-				CKL_HIP(hipMemcpyAsync(o + off_codes, e.d_codes_out.p, cr.total, hipMemcpyDeviceToHost, e.stream_copy));
-				if (labels_stay) {
-					CKL_HIP(hipMemcpyAsync(o + off_labels, e.d_labels_bin.p, label_bytes, hipMemcpyDeviceToHost, e.stream_copy));
-					CKL_HIP(hipMemcpyAsync(o + off_tail, e.d_labels_crc.p, 4, hipMemcpyDeviceToHost, e.stream_copy));
-				}
-				e.host_copy_pending = true;
-			}
-			else CKL_HIP(hipMemcpyAsync(o + off_codes, e.d_codes_out.p, cr.total, hipMemcpyDeviceToHost, s));
-		}
+		write_frame(o, head, l, cr.code_len, stored_model);
+		for (int64_t z = 0; z < sz; z++) put4(o + l.off_tail + 4 + 4ull * z, side.flat.crcs[z]);
+		put4(o + l.off_tail, side.labels_crc);
+		assemble(e, o, head, l, side.labels_stay);
 		ht.mark("assembly");
 		CKL_HIP(hipEventRecord(e.ev1, s));
 		CKL_HIP(hipStreamSynchronize(s));
@@ -2687,7 +2078,7 @@ void encode_typed(ckl_encoder& e, const LABEL* labels, int64_t sx, int64_t sy, i
 	}
 	if (e.label_src) e.host_marks = ht.marks;      // recompress (ckl_recompress.hip) folds them into its own line
 	*out = o;
-	*out_len = total;
+	*out_len = l.total;
 }
 
 }  // namespace
@@ -2785,28 +2176,19 @@ void reencode_markov(const uint8_t* buf, uint64_t n, int markov_order, int devic
 	else cr.code_len.assign(sz, 0);
 
 	// assembly (crackle.hpp:935-981)
-	const uint64_t off_model = off_labels + head.num_label_bytes;
-	const uint64_t off_codes = off_model + stored_model.size();
-	const uint64_t off_tail = off_codes + cr.total;
-	const uint64_t total = off_tail + tail_bytes;
-	uint8_t* o = static_cast<uint8_t*>(host_out_alloc(total));
+	const StreamLayout l = stream_layout(head, stored_model.size(), cr.total);
+	uint8_t* o = static_cast<uint8_t*>(host_out_alloc(l.total));
 	try {
-		if (cr.total) CKL_HIP(hipMemcpyAsync(o + off_codes, enc.e->d_codes_out.p, cr.total, hipMemcpyDeviceToHost, enc.e->stream));
-		std::vector<uint8_t> hb;
-		head.write(hb);
-		memcpy(o, hb.data(), hb.size());
-		auto put4 = [&](uint64_t at, uint32_t v) { for (int b = 0; b < 4; b++) o[at + b] = static_cast<uint8_t>((v >> (8 * b)) & 0xFF); };
-		for (uint64_t z = 0; z < sz; z++) put4(off_index + 4 * z, cr.code_len[z]);
-		if (!v0) put4(off_index + 4 * sz, crc32c(o + off_index, 4 * sz));
-		memcpy(o + off_labels, buf + off_labels, head.num_label_bytes);
-		if (!stored_model.empty()) memcpy(o + off_model, stored_model.data(), stored_model.size());
-		if (tail_bytes) memcpy(o + off_tail, buf + old_tail, tail_bytes);
+		if (cr.total) CKL_HIP(hipMemcpyAsync(o + l.off_codes, enc.e->d_codes_out.p, cr.total, hipMemcpyDeviceToHost, enc.e->stream));
+		write_frame(o, head, l, cr.code_len, stored_model);
+		memcpy(o + l.off_labels, buf + l.off_labels, head.num_label_bytes);
+		if (tail_bytes) memcpy(o + l.off_tail, buf + old_tail, tail_bytes);
 		if (cr.total) CKL_HIP(hipStreamSynchronize(enc.e->stream));
 		lap("assembly");
 	}
 	catch (...) { host_out_free(o); throw; }
 	*out = o;
-	*out_len = total;
+	*out_len = l.total;
 }
 
 }  // namespace
@@ -2995,11 +2377,10 @@ static uint32_t* encoder_components(ckl_encoder* e, const void* labels_device, i
 	FlatResult fr;
 	if (!planes_cached(*e, labels_device, sx, sy, sz)) planes_pass_any(*e, labels_device, sx, sy, sz, nullptr);
 	flat_enqueue(*e, labels_device, sx, sy, sz, true, false);      // (the paint below reads the run tables)
-	with_label_type(e->dtype_bytes, [&](auto t) { flat_collect(*e, static_cast<const typename decltype(t)::type*>(labels_device), sx, sy, sz, fr); });
+	flat_collect(*e, labels_device, e->dtype_bytes, sx, sy, sz, fr);
 	if (fr.total + id_base > 0xFFFFFFFFull) throw Error(CKL_ERR_RUNTIME, "crackle_amd: too many components");
-	hipStream_t s2 = e->stream2;
 	if (!cc_device) { e->d_cc_volume.ensure(voxels); cc_device = e->d_cc_volume.p; }
-	launch_paint_components(s2, plane_v(*e), e->row_words, e->plane_words, sx, sy, sz, e->d_word_base.p, e->d_rbase.p, e->d_run_cc.p, e->d_comp_off.p, id_base, cc_device);
+	paint_components(*e, sx, sy, sz, id_base, cc_device);
 	for (int64_t z = 0; z < sz; z++) ncomp_host[z] = fr.ncomp[z];
 	return cc_device;
 }

@@ -1,6 +1,7 @@
-// The encode session (created and run by ckl_encode.hip) and what the pin stage (ckl_encode_pins.hip) and the road
-// from a decode session's tables (ckl_recompress.hip) need of it: the session's streams and scratch, the small
-// transfers, the host timer, enter(), and that road's door (planes_adopt, encode_from_planes).
+// The encode session (created and run by ckl_encode.hip) and what the flat label stage (ckl_encode_labels.hip), the pin
+// stage (ckl_encode_pins.hip) and the road from a decode session's tables (ckl_recompress.hip) need of it: the session's
+// streams and scratch, the label stage's own part of it (LabelStage), the small transfers, the host timer, enter(), and
+// that road's door (planes_adopt, encode_from_planes).
 #pragma once
 
 #include "ckl_common.hpp"
@@ -10,6 +11,33 @@
 
 struct VolumeStats { uint64_t max_label = 0, pairs = 0, first = 0, last = 0; };
 namespace ckl { namespace dev { struct RunLabels; } }
+
+// What the flat label stage keeps in the session and nobody else names (ckl_encode_labels.hip).  What the stage leaves
+// for others (d_mapping, d_labels_bin, d_slice_err2) stands in the session itself.
+struct LabelStage {
+	template <typename T> using DevBuf = ckl::DevBuf<T>;
+
+	// run-based CCL (ckl_runs.hpp)
+	DevBuf<uint64_t> d_rbase, d_comp_off;
+	DevBuf<uint32_t> d_rcap, d_word_base, d_parent, d_run_start, d_run_cc, d_comp_pix, d_nruns, d_ncomp, d_idbits, d_blk_roots;
+	DevBuf<uint16_t> d_run_local;
+	DevBuf<uint32_t> d_G, d_crc_acc;
+	DevBuf<uint32_t> d_flat_report;     // [4][nslices] + 1: ncomp | crc_acc | idbits | slice_err2 (views: the three above and the session's d_slice_err2) | the strip kernels' overflow word
+	uint64_t g_table_pixels = 0;                // slice size the G table was built for
+	DevBuf<uint64_t> d_sorted, d_uniq, d_label_hash, d_label_list;      // the label table (flat_section)
+	DevBuf<uint32_t> d_n_uniq, d_uniq_blk;
+	std::vector<uint64_t> h_rbase;
+	std::vector<uint32_t> h_rcap;
+	std::vector<uint64_t> h_comp_off;  // first component of every slice: stays alive while its upload is in flight
+	// flat labels from the strip kernels (ckl_strips.hpp; flat_enqueue / flat_collect): per-strip tables, then the labels
+	// of every slice's components in a slot of flat_resolve_cap entries
+	DevBuf<uint16_t> s_run_lid, s_seam_first, s_seam_last;
+	DevBuf<uint32_t> s_sc_w, s_sc_first, s_strip_nruns, s_strip_nsc;
+	DevBuf<uint64_t> d_label_slots;
+	uint32_t flat_nstrips = 0, flat_strip_rows = 0, flat_strip_cap = 0, flat_resolve_cap = 0;
+	int max_lds = 0;                   // the device's LDS per workgroup (asked once)
+	bool flat_strips = false;          // the label stage that is enqueued runs on the strip kernels
+};
 
 struct ckl_encoder {
 	template <typename T> using DevBuf = ckl::DevBuf<T>;
@@ -26,7 +54,7 @@ struct ckl_encoder {
 	DevBuf<unsigned long long> d_stats;
 	DevBuf<uint4> d_adjm;                        // crack graph in micro-tiles (ckl_trail.hpp)
 	DevBuf<uint32_t> d_slice_err;
-	DevBuf<uint64_t> d_cbase, d_sbase, d_kbase, d_pbase, d_bbase, d_out_off, d_comp_off;
+	DevBuf<uint64_t> d_cbase, d_sbase, d_kbase, d_pbase, d_bbase, d_out_off;
 	DevBuf<uint32_t> d_ccap, d_scap, d_kcap;
 	DevBuf<uint8_t> d_crack_tables;               // packed block behind the per-slice base / capacity tables of crack_pass
 	DevBuf<uint8_t> d_cp, d_fcode, d_dcode, d_payload, d_boc, d_codes_out, d_model;
@@ -50,23 +78,18 @@ struct ckl_encoder {
 	DevBuf<uint32_t> d_chain_node, d_chain_off, d_chain_clen, d_chain_order, d_chain_dst, d_chain_vstart;
 	DevBuf<uint32_t> d_n_chains, d_n_raw, d_n_valid, d_payload_len, d_boc_len;
 	DevBuf<uint32_t> d_hist;
-	// label planes + run-based CCL (ckl_runs.hpp)
+	// label planes
 	DevBuf<uint32_t> d_planes, d_count_vh;
 	uint32_t row_words = 0;
 	uint64_t plane_words = 0;
 	std::vector<uint32_t> count_v, count_h;     // differing neighbour pairs per slice (host copy)
-	DevBuf<uint64_t> d_rbase;
-	DevBuf<uint32_t> d_rcap, d_word_base, d_parent, d_run_start, d_run_cc, d_comp_pix, d_nruns, d_ncomp, d_idbits, d_blk_roots;
-	DevBuf<uint16_t> d_run_local;
-	DevBuf<uint32_t> d_G, d_crc_acc;
-	DevBuf<uint32_t> d_flat_report;     // [4][nslices] + 1: ncomp | crc_acc | idbits | slice_err2 (views above) | the strip kernels' overflow word
-	uint64_t g_table_pixels = 0;                // slice size the G table was built for
-	DevBuf<uint64_t> d_mapping, d_sorted, d_uniq, d_label_hash, d_label_list;
+	LabelStage ls;                               // the flat label stage's own tables and plan (ckl_encode_labels.hip)
+	DevBuf<uint64_t> d_mapping;                  // the label of every component, slice after slice (flat_collect, the pin stage)
 	DevBuf<uint32_t> d_cc_volume;                // global component id of every voxel (pin encoding only)
 	DevBuf<uint32_t> d_pin_kept, d_pin_u32;      // pin passes (ckl_pins_dev.hpp): kept-run marks (uint16 per voxel), per-component depths
 	DevBuf<uint8_t> d_pin_tables;                // per-row label tables of k_pin_dedup
 	DevBuf<uint64_t> d_pin_u64;                  // per-component keys
-	DevBuf<uint32_t> d_slice_err2, d_n_uniq, d_uniq_blk;
+	DevBuf<uint32_t> d_slice_err2;               // the label stage's error word per slice (a view of its report), the pin stage's error word
 	DevBuf<uint8_t> d_labels_bin;                // the flat label section, assembled on device
 	// label planes left by ckl_encoder_stats for the ckl_encoder_run that follows on the same
 	// volume (the sharded encoder: stats -> all-gather -> run with the agreed formats)
@@ -83,17 +106,6 @@ struct ckl_encoder {
 	std::vector<std::pair<const char*, double>> host_marks;      // the host timer's marks of that run: read by ckl_recompress.hip's profile line (CKL_PROFILE), by nothing else
 	VolumeStats planes_stats;          // max / pairs of the volume the cached planes were built from
 	int64_t planes_dims[3] = { 0, 0, 0 };
-	std::vector<uint64_t> h_rbase;
-	std::vector<uint32_t> h_rcap;
-	std::vector<uint64_t> h_comp_off;  // first component of every slice: stays alive while its upload is in flight
-	// flat labels from the strip kernels (ckl_strips.hpp; flat_enqueue / flat_collect): per-strip tables, then the labels
-	// of every slice's components in a slot of flat_resolve_cap entries
-	DevBuf<uint16_t> s_run_lid, s_seam_first, s_seam_last;
-	DevBuf<uint32_t> s_sc_w, s_sc_first, s_strip_nruns, s_strip_nsc;
-	DevBuf<uint64_t> d_label_slots;
-	uint32_t flat_nstrips = 0, flat_strip_rows = 0, flat_strip_cap = 0, flat_resolve_cap = 0;
-	int max_lds = 0;                   // the device's LDS per workgroup (asked once)
-	bool flat_strips = false;          // the label stage that is enqueued runs on the strip kernels
 	// trail graph (ckl_trail.hpp)
 	std::vector<uint32_t> count_special, count_corner;
 	DevBuf<uint32_t> d_plane_partial, t_blk_special, t_blk_corner;

@@ -8,7 +8,7 @@
 //   k_component_labels_from_runs   the label of every component of the NEW planes, from its first pixel
 //                                  (what k_mapping_comps and k_slice_resolve_enc read from the volume)
 // The first two are launched by the road itself (ckl_recompress.hip), the third by the encoder's label stage
-// (ckl_encode.hip): two units see this header, so its kernels are static.
+// (flat_launch_resolve / flat_collect, ckl_encode_labels.hip): two units see this header, so its kernels are static.
 #pragma once
 
 #include "ckl_run_types.hpp"

@@ -175,7 +175,7 @@ __device__ __forceinline__ void raster_half_record(
 // k_slice_resolve read them there); otherwise they are read from the planes k_decode_cracks left.
 // The body works in `lds` (kStripCclWords 32-bit words, 16-byte aligned) on strip k of slice zi, so that
 // the caller owns the block (a launch mixing stages of different slice groups was tried: DESIGN.md section 10).
-// ENC: the encoder's variant (k_strip_ccl_enc, ckl_encode.hip) — the first pixel of every strip component (slice-linear: the start of
+// ENC: the encoder's variant (k_strip_ccl_enc, ckl_encode_labels.hip) — the first pixel of every strip component (slice-linear: the start of
 // its root run, the first of its runs) goes to sc_cc, where the resolve finds the component's label; row_run, which
 // only pins and the paint read, is not written.
 // CAP: runs the tables hold (the encoder's strips share a CU's LDS with the crack trail's walk and take smaller ones)

@@ -1,5 +1,5 @@
-"""Volumes aimed at the size decisions of the encoder's flat label table (crackle_amd/csrc/ckl_encode.hip: flat_section
-and its kernels, crc32c_device, k_copy_bytes, k_code_offsets).  Plain numpy; shared by the CPU test that pins every
+"""Volumes aimed at the size decisions of the encoder's flat label table (crackle_amd/csrc/ckl_encode_labels.hip: flat_section
+and its kernels; ckl_encode.hip: crc32c_device, k_copy_bytes, k_code_offsets).  Plain numpy; shared by the CPU test that pins every
 case against the checker's own stream (tests/test_label_table_volumes_cpu.py) and by the GPU tests that run the kernels
 on them (tests/test_gpu_label_table.py).
 

@@ -1,5 +1,5 @@
 """GPU tests of the encoder's label stage on the strip kernels (crackle_amd/csrc/ckl_strips.hpp: strip_ccl_body and
-slice_resolve_body in their encoder modes; ckl_encode.hip: k_strip_ccl_enc, k_gather_slots, flat_enqueue /
+slice_resolve_body in their encoder modes; ckl_encode_labels.hip: k_strip_ccl_enc, k_gather_slots, flat_enqueue /
 flat_collect) and of its hand-over to the run pipeline of ckl_runs.hpp.
 
 The check throughout: crackle_amd.compress(arr, ...) equals the checker's compress byte for byte, once on the default

@@ -1,6 +1,6 @@
-"""GPU tests of the encoder's flat label table at its own size thresholds (crackle_amd/csrc/ckl_encode.hip:
+"""GPU tests of the encoder's flat label table at its own size thresholds (crackle_amd/csrc/ckl_encode_labels.hip:
 flat_section with k_label_hash_*, k_pad_copy_u64, k_bitonic_first / step / step2 / local, k_unique_*, k_flat_section;
-crc32c_device with k_crc32c_pieces / k_crc32c_fold; k_copy_bytes; k_code_offsets).
+ckl_encode.hip: crc32c_device with k_crc32c_pieces / k_crc32c_fold; k_copy_bytes; k_code_offsets).
 
 The volumes come from tests/label_table_volumes.py, which aims N (components), U (labels) and L (label section bytes) at
 the numbers the code decides by; tests/test_label_table_volumes_cpu.py pins every one of them against the port on the

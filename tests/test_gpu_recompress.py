@@ -1,5 +1,5 @@
 """GPU tests of crackle_amd.recompress (ckl_recompress: the decoder's run tables -> k_label_planes_from_runs -> the
-encoder's crack and label stages, crackle_amd/csrc/ckl_recompress.hpp, ckl_recompress.hip and ckl_encode.hip).
+encoder's crack and label stages, crackle_amd/csrc/ckl_recompress.hpp, ckl_recompress.hip, ckl_encode.hip and ckl_encode_labels.hip).
 
 The check throughout: recompress(stream, ...) equals the checker's compress of the volume the stream decodes to,
 byte for byte, under the requested markov order (default: the stream's), once on the default label path and once

@@ -14,7 +14,7 @@ comparing the volume with numpy.
 Where the dynamic LDS of a kernel depends on the input, a kind has inputs on both sides of 64 KiB (lds_sides): the
 limit of such a kernel is a property of the process, so the large input of one thread and the small one of another
 are what a per-call setting would get wrong.  The host rules are restated here from the code (ckl_encode.hip:
-trail_walk_lds, the clds line of crack_pass, emit_plan, flat_resolve_cap; ckl_operations.hip: lds_comps *
+trail_walk_lds, the clds line of crack_pass, emit_plan; ckl_encode_labels.hip: flat_resolve_cap; ckl_operations.hip: lds_comps *
 kStatsBytesPerComp, vis_words) for a device with MAX_LDS bytes of LDS per workgroup; the GPU test checks that figure
 and compares the two rules tests/test_gpu_consumer_edges.py restates as well with that file's functions.
 

@@ -18,6 +18,7 @@ CKL_OK, CKL_ERR_FORMAT, CKL_ERR_RUNTIME, CKL_ERR_ARG, CKL_ERR_NO_DEVICE, CKL_ERR
 MEM_HOST, MEM_DEVICE = 0, 1
 CKL_DUST_BINARY_IMAGE, CKL_DUST_INVERT = 1, 2
 CKL_ERODE_KEEP_BORDER = 1
+CKL_COMBINE_OVERLAY, CKL_COMBINE_KEEP_WHERE, CKL_COMBINE_DROP_WHERE = 0, 1, 2
 
 
 class HeaderInfo(C.Structure):
@@ -125,6 +126,7 @@ EXPORTS = {
   "ckl_erode": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_dilate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_downsample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+  "ckl_combine": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_decoder_crack_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
   "ckl_zsplit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
   "ckl_encoder_defer_codes": (C.c_int, [C.c_void_p, C.c_int]),

@@ -260,6 +260,16 @@ class CrackleArray:
     other_binary = other.binary if isinstance(other, CrackleArray) else other
     return operations.overlaps(self.binary, other_binary, device=self.device)
 
+  def overlay(self, other: Union["CrackleArray", bytes]) -> "CrackleArray":
+    """`other` where it is not 0, this array elsewhere (operations.overlay)."""
+    other_binary = other.binary if isinstance(other, CrackleArray) else other
+    return CrackleArray(operations.overlay(self.binary, other_binary, device=self.device), self.device)
+
+  def mask_by(self, other: Union["CrackleArray", bytes], invert: bool = False) -> "CrackleArray":
+    """This array where `other` is not 0 (invert: where it is 0), 0 elsewhere (operations.mask_by)."""
+    other_binary = other.binary if isinstance(other, CrackleArray) else other
+    return CrackleArray(operations.mask_by(self.binary, other_binary, invert=invert, device=self.device), self.device)
+
   def connected_components(self, connectivity: int = 26, binary_image: bool = False, return_mapping: bool = False):
     out = operations.connected_components(self.binary, connectivity=connectivity, binary_image=binary_image, return_mapping=return_mapping, device=self.device)
     if return_mapping:

@@ -1,8 +1,10 @@
 // crackle.operations.recompress (crackle/operations.py:664-857 decodes slabs to voxels and compresses them again), and
-// erode, dilate and downsample, which are the same road with another volume at its end.  Here no voxel exists anywhere:
+// erode, dilate, downsample and combine, which are the same road with another volume at its end (combine: of two streams,
+// through a sibling of recompress() below).  Here no voxel exists anywhere:
 // a TABLES run of the decoder leaves the runs of every slice and the label of every component, a plane stage writes the
 // encoder's planes and their counts from them (plain: ckl_recompress.hpp, eroded: ckl_erode.hpp, dilated:
-// ckl_dilate.hpp, pooled: ckl_downsample.hpp, the one whose volume has another shape than the decoder's), and
+// ckl_dilate.hpp, pooled: ckl_downsample.hpp, the one whose volume has another shape than the decoder's, combined:
+// ckl_combine.hpp, the one with two decoders), and
 // encode_from_planes (ckl_encoder.hpp) goes on as the encoder does from cached planes, with its label stage reading the
 // same tables.  The bytes are those of compress(edit(decompress(stream)), markov_model_order).
 #include "ckl_encoder.hpp"
@@ -11,6 +13,7 @@
 #include "ckl_erode.hpp"
 #include "ckl_dilate.hpp"
 #include "ckl_downsample.hpp"
+#include "ckl_combine.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -22,10 +25,11 @@ namespace {
 
 // what a call does to the labels on their way through
 struct LabelEdit {
-	enum Kind { NONE, ERODE, DILATE, POOL } kind = NONE;
+	enum Kind { NONE, ERODE, DILATE, POOL, COMBINE } kind = NONE;
 	int connectivity = 0;          // ERODE, DILATE: 6, 18, 26
 	bool keep_border = false;      // ERODE: neighbours outside the volume are ignored
 	int fx = 1, fy = 1, fz = 1;    // POOL: (2, 2, 1) or (2, 2, 2)
+	int rule = 0;                  // COMBINE: CKL_COMBINE_*
 };
 
 // per kind: the operation's name, and the two fields of its CKL_PROFILE line that carry the kind in their names
@@ -35,6 +39,7 @@ constexpr EditNames kEditNames[] = {
 	{ "erode", "keep_planes", "k_erode_device" },
 	{ "dilate", "gain_planes", "k_dilate_device" },
 	{ "downsample", "pool_planes", "k_pool_device" },
+	{ "combine", "merge_planes", "k_combine_device" },
 };
 
 // Device scratch of one call's edit.  What a plane stage returns points into it and is read by the encoder's label
@@ -47,16 +52,17 @@ struct EditScratch {
 	DevBuf<uint32_t> pool_cut;                 // ckl_downsample.hpp's plane of cuts, [osz][output plane_words]
 	DevBuf<uint64_t> pool_cut_off;             // [osz][output plane_words]
 	DevBuf<uint64_t> pool_label;               // [cuts]
+	// (ckl_combine.hpp's cuts, their offsets and labels stand in the three pool_* buffers: the same triple at the volume's own shape)
 };
 
 // what the plane stages launch with
 struct Road {
-	ckl_decoder& d;                    // after its TABLES run
+	ckl_decoder& d;                    // after its TABLES run (COMBINE: the first stream's)
 	ckl_encoder& e;                    // planes_adopt() done: the stages write plane_v / plane_h and d_count_vh [3][ns]
 	hipStream_t s;                     // the encode session's
 	uint32_t ns;                       // the ENCODER's slices (POOL: not the decoder's)
 	dim3 word_grid;                    // a thread per 32-pixel word of the encoder's planes
-	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's and ckl_downsample's cursor
+	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's, ckl_downsample's and ckl_combine's cursor
 };
 
 // the decode session's tables as the kernels of this road read them
@@ -69,11 +75,12 @@ RunLabels run_labels(const ckl_decoder& d) {
 	return src;
 }
 
-// one label per run, at the runs' own bases (in PAINT's scratch of the decode session): what erode and dilate read
-const uint64_t* gather_run_labels(const Road& r, const RunLabels& src) {
-	r.d.d_run_label.ensure(r.d.rtot);
-	hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((r.d.max_rcap + kBlock - 1) / kBlock + 1, 256), r.d.nslices), dim3(kBlock), 0, r.s, src, r.d.d_run_label.p);
-	return r.d.d_run_label.p;
+// one label per run of session d (src: its tables), at the runs' own bases (in PAINT's scratch of that session), on
+// stream s: what erode, dilate, downsample and combine read
+const uint64_t* gather_run_labels(ckl_decoder& d, const RunLabels& src, hipStream_t s) {
+	d.d_run_label.ensure(d.rtot);
+	hipLaunchKernelGGL(k_erode_run_labels, dim3(std::min<uint32_t>((d.max_rcap + kBlock - 1) / kBlock + 1, 256), d.nslices), dim3(kBlock), 0, s, src, d.d_run_label.p);
+	return d.d_run_label.p;
 }
 
 // The three plane stages.  Each only launches; what the label stage needs beside the tables is what it hands back:
@@ -130,6 +137,23 @@ unsigned long long pooled_planes(const Road& r, RunLabels& src, const uint64_t* 
 	return cuts;
 }
 
+// Leaves the combined triple in src (the first stream's tables; the label stage reads the triple alone); counters[0]
+// takes the largest combined label.  The two sessions' planes agree in layout (combine() has checked).
+void combined_planes(const Road& r, RunLabels& src, const CombineSide& a, const CombineSide& b, int rule, EditScratch& scratch) {
+	const size_t pw = r.e.plane_words * r.ns;
+	scratch.pool_cut.ensure(pw);
+	scratch.pool_cut_off.ensure(pw);
+	hipLaunchKernelGGL(k_combine_cuts, r.word_grid, dim3(kBlock), 0, r.s, a.g, b.g, scratch.pool_cut.p, scratch.pool_cut_off.p, r.counters + 1);
+	const unsigned long long cuts = download(r.counters + 1, 1, r.s)[0];      // the host sizes the cuts' labels (every word has a cut: not 0)
+	scratch.pool_label.ensure(cuts);
+	auto* const labels = rule == CKL_COMBINE_OVERLAY ? k_combine_labels<CKL_COMBINE_OVERLAY> : rule == CKL_COMBINE_KEEP_WHERE ? k_combine_labels<CKL_COMBINE_KEEP_WHERE> : k_combine_labels<CKL_COMBINE_DROP_WHERE>;
+	hipLaunchKernelGGL(labels, r.word_grid, dim3(kBlock), 0, r.s, a, b, scratch.pool_cut.p, scratch.pool_cut_off.p, scratch.pool_label.p, r.counters);
+	src.pool_cut = scratch.pool_cut.p; src.pool_off = scratch.pool_cut_off.p; src.pool_label = scratch.pool_label.p;
+	src.pool_sx = a.g.sx; src.pool_sy = a.g.sy; src.pool_row_words = a.g.row_words; src.pool_plane_words = a.g.plane_words;
+	const PoolGeom same = { 1u, r.ns, a.g.sx, a.g.sy, a.g.row_words, a.g.plane_words };
+	hipLaunchKernelGGL(k_pool_planes, r.word_grid, dim3(kBlock), 0, r.s, src, same, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
+}
+
 // lib::pixel_pairs (lib.hpp:249-256): equal neighbours in x-fastest order — inside the rows every pair that V does not
 // mark, and the wrap-arounds the plane writer counted.  counts: [3][ns] bits of V | bits of H | wrap pairs
 VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_label, int64_t sx, int64_t sy, uint32_t ns) {
@@ -139,8 +163,8 @@ VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_
 	return st;
 }
 
-// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the four operations read it).  extra: DILATE's
-// gained pixels, POOL's pieces
+// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the five operations read it).  extra: DILATE's
+// gained pixels, POOL's and COMBINE's pieces
 void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, const ckl_encoder& e, float ms_kernel, unsigned long long extra) {
 	double graph = 0, cracks = 0, labels = 0, assembly = 0;
 	for (const auto& m : e.host_marks) {
@@ -153,7 +177,7 @@ void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, co
 	const EditNames& names = kEditNames[edit.kind];
 	char tail[40] = "";
 	if (edit.kind == LabelEdit::DILATE) snprintf(tail, sizeof(tail), " gained=%llu", extra);
-	if (edit.kind == LabelEdit::POOL) snprintf(tail, sizeof(tail), " pieces=%llu", extra);
+	if (edit.kind == LabelEdit::POOL || edit.kind == LabelEdit::COMBINE) snprintf(tail, sizeof(tail), " pieces=%llu", extra);
 	fprintf(stderr, "[ckl %s host ms] tables=%.2f %s=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f %s=%.3f%s\n",
 		names.op, ms_tables, names.planes_field, ms_planes, graph, cracks, labels, assembly, names.device_field, ms_kernel, tail);
 }
@@ -165,7 +189,7 @@ Header checked_header(const uint8_t* buf, uint64_t n, int markov_order, const La
 		if (edit.fx != 2 || edit.fy != 2 || (edit.fz != 1 && edit.fz != 2))
 			throw Error(CKL_ERR_ARG, "crackle_amd: downsample: factor must be (2, 2, 1) or (2, 2, 2). Got: (" + std::to_string(edit.fx) + ", " + std::to_string(edit.fy) + ", " + std::to_string(edit.fz) + ")");
 	}
-	else if (edit.kind != LabelEdit::NONE && edit.connectivity != 6 && edit.connectivity != 18 && edit.connectivity != 26)
+	else if ((edit.kind == LabelEdit::ERODE || edit.kind == LabelEdit::DILATE) && edit.connectivity != 6 && edit.connectivity != 18 && edit.connectivity != 26)
 		throw Error(CKL_ERR_ARG, std::string("crackle_amd: ") + kEditNames[edit.kind].op + ": connectivity must be 6, 18 or 26. Got: " + std::to_string(edit.connectivity));
 	if (n < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n));
 	const Header head = Header::parse(buf, n);
@@ -223,7 +247,7 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, co
 	CKL_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), e.stream));
 	const Road r = { d, e, e.stream, ns, dim3(static_cast<uint32_t>((plane_words + kBlock - 1) / kBlock), ns), counters.p };
 	CKL_HIP(hipEventRecord(e.evd0, r.s));
-	const uint64_t* run_label = edit.kind == LabelEdit::NONE ? nullptr : gather_run_labels(r, src);
+	const uint64_t* run_label = edit.kind == LabelEdit::NONE ? nullptr : gather_run_labels(d, src, r.s);
 	unsigned long long gained = 0;
 	if (edit.kind == LabelEdit::ERODE) src.keep = eroded_planes(r, src, run_label, edit, scratch);
 	else if (edit.kind == LabelEdit::DILATE) gained = dilated_planes(r, src, run_label, edit, scratch);
@@ -245,6 +269,78 @@ void recompress(const uint8_t* buf, uint64_t n, int markov_order, int device, co
 	unsigned long long pieces = static_cast<unsigned long long>(sy) * ns;
 	for (uint32_t zi = 0; zi < ns; zi++) pieces += counts[zi];
 	if (getenv("CKL_PROFILE")) print_profile(edit, ms_between(t_start, t_tables), ms_between(t_tables, t_planes), e, ms_kernel, pool ? pieces : gained);
+}
+
+// what the kernels of ckl_combine.hpp read of session d: its tables and one label per run, gathered on stream s
+CombineSide combine_side(ckl_decoder& d, hipStream_t s) {
+	const RunLabels t = run_labels(d);
+	return { t.g, t.word_base, t.rbase, t.nruns, gather_run_labels(d, t, s) };
+}
+
+const char* combine_name(int rule) { return rule == CKL_COMBINE_OVERLAY ? "overlay" : "mask_by"; }
+
+// recompress()'s sibling for two streams of one shape: the same road from the plane stage on, with two decode sessions,
+// a then b, alive to its end.  The output's data width is a's, for CKL_COMBINE_OVERLAY the larger of the two.
+void combine(const uint8_t* buf_a, uint64_t n_a, const uint8_t* buf_b, uint64_t n_b, int rule, int markov_order, int device, uint8_t** out, uint64_t* out_len) {
+	LabelEdit edit;
+	edit.kind = LabelEdit::COMBINE; edit.rule = rule;
+	if (rule != CKL_COMBINE_OVERLAY && rule != CKL_COMBINE_KEEP_WHERE && rule != CKL_COMBINE_DROP_WHERE)
+		throw Error(CKL_ERR_ARG, "crackle_amd: combine: unknown rule: " + std::to_string(rule));
+	if (n_a < Header::kBytesV0 || n_b < Header::kBytesV0) throw Error(CKL_ERR_FORMAT, "crackle: Input too small to be a valid stream. Bytes: " + std::to_string(n_a < Header::kBytesV0 ? n_a : n_b));
+	const Header shape_a = Header::parse(buf_a, n_a), shape_b = Header::parse(buf_b, n_b);
+	if (shape_a.sx != shape_b.sx || shape_a.sy != shape_b.sy || shape_a.sz != shape_b.sz)
+		throw Error(CKL_ERR_ARG, std::string("crackle_amd: ") + combine_name(rule) + ": the volumes differ in shape: " + std::to_string(shape_a.sx) + " x " + std::to_string(shape_a.sy) + " x " + std::to_string(shape_a.sz)
+			+ " and " + std::to_string(shape_b.sx) + " x " + std::to_string(shape_b.sy) + " x " + std::to_string(shape_b.sz));
+	uint64_t order = 0, order_b = 0;
+	const Header head = checked_header(buf_a, n_a, markov_order, edit, order);
+	const Header head_b = checked_header(buf_b, n_b, 0, edit, order_b);      // (the order is a's or the caller's)
+	const int data_width = rule == CKL_COMBINE_OVERLAY ? std::max(head.data_width, head_b.data_width) : head.data_width;
+	const int64_t sx = head.sx, sy = head.sy, sz = head.sz;
+	if (head.voxels() == 0) {
+		hand_out(header_bytes(stream_header(data_width, sx, sy, sz, VolumeStats(), false, head.fortran_order, order, nullptr)), OutAlloc::MALLOC, out, out_len);
+		return;
+	}
+	select_device(device);      // (what came before needs none: refusals and streams without voxels are the host's)
+	const auto t_start = Clock::now();
+	const DecoderPtr dec_a = tables_session(buf_a, n_a, device);      // (a damaged slice of a raises before b is looked at)
+	const DecoderPtr dec_b = tables_session(buf_b, n_b, device);
+	const auto t_tables = Clock::now();
+	RunLabels src = run_labels(*dec_a);
+	const RunGeom gb = run_geom(*dec_b);
+	if (src.g.sx != gb.sx || src.g.sy != gb.sy || src.g.row_words != gb.row_words || src.g.plane_words != gb.plane_words || dec_a->nslices != dec_b->nslices)
+		throw Error(CKL_ERR_RUNTIME, std::string("crackle_amd: ") + combine_name(rule) + ": the sessions' crack planes differ in layout");
+
+	DevBuf<unsigned long long> counters;
+	EditScratch scratch;
+	ckl_encoder* raw = nullptr;
+	if (ckl_encoder_create(sx, sy, sz, data_width, device, &raw) != CKL_OK) throw Error(CKL_ERR_RUNTIME, ckl_last_error());
+	const EncoderPtr enc(raw);
+	ckl_encoder& e = *enc;
+	enter(&e);
+	const uint32_t ns = static_cast<uint32_t>(sz);
+	const uint32_t row_words = static_cast<uint32_t>((sx + 31) / 32);
+	const uint64_t plane_words = static_cast<uint64_t>(row_words) * sy;
+	if (row_words != src.g.row_words || plane_words != src.g.plane_words || ns != dec_a->nslices)
+		throw Error(CKL_ERR_RUNTIME, std::string("crackle_amd: ") + combine_name(rule) + ": the session's crack planes are not the volume's");
+	planes_adopt(e, row_words, plane_words, ns, 3);
+	counters.ensure(2);
+	CKL_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), e.stream));
+	const Road r = { *dec_a, e, e.stream, ns, dim3(static_cast<uint32_t>((plane_words + kBlock - 1) / kBlock), ns), counters.p };
+	CKL_HIP(hipEventRecord(e.evd0, r.s));
+	const CombineSide side_a = combine_side(*dec_a, r.s), side_b = combine_side(*dec_b, r.s);
+	combined_planes(r, src, side_a, side_b, rule, scratch);
+	CKL_HIP(hipEventRecord(e.evd1, r.s));
+	const std::vector<uint32_t> counts = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), r.s);
+	const VolumeStats st = stats_from_counts(counts, download(counters.p, 1, r.s)[0], sx, sy, ns);      // (k_combine_labels has taken the largest combined label)
+	float ms_kernel = 0.f;
+	CKL_HIP(hipEventElapsedTime(&ms_kernel, e.evd0, e.evd1));
+	const auto t_planes = Clock::now();
+
+	encode_from_planes(e, src, sx, sy, sz, data_width, head.fortran_order, order, st, counts, out, out_len);
+	// the combined volume's runs, counted as POOL counts its pieces: one per row and one more per bit of V
+	unsigned long long pieces = static_cast<unsigned long long>(sy) * ns;
+	for (uint32_t zi = 0; zi < ns; zi++) pieces += counts[zi];
+	if (getenv("CKL_PROFILE")) print_profile(edit, ms_between(t_start, t_tables), ms_between(t_tables, t_planes), e, ms_kernel, pieces);
 }
 
 }  // namespace
@@ -281,6 +377,14 @@ int ckl_downsample(const uint8_t* buf, uint64_t n, int fx, int fy, int fz, int f
 		LabelEdit edit;
 		edit.kind = LabelEdit::POOL; edit.fx = fx; edit.fy = fy; edit.fz = fz;
 		recompress(buf, n, markov_model_order, device, edit, out, out_len);
+	});
+}
+
+int ckl_combine(const uint8_t* buf_a, uint64_t n_a, const uint8_t* buf_b, uint64_t n_b, int rule, int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len) {
+	return guard([&] {
+		if (!buf_a || !buf_b || !out || !out_len) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: combine: flags must be 0");
+		combine(buf_a, n_a, buf_b, n_b, rule, markov_model_order, device, out, out_len);
 	});
 }
 

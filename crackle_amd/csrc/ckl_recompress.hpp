@@ -35,7 +35,8 @@ struct RunLabels {
 	// ckl_downsample.hpp: the encoder's volume is the pooled one, of another shape than the decoder's.  pool_cut
 	// [osz][pool_plane_words]: bit x set where pixel x of the word's row may change its pooled label (bit 0 of every word
 	// is set); the pixel carries pool_label[pool_off[its word] + the set bits of the word at or below it - 1] (nullptr: no
-	// pooling, the encoder's volume has the decoder's shape)
+	// pooling, the encoder's volume has the decoder's shape).  The triple has two producers: ckl_downsample.hpp (the pooled
+	// shape) and ckl_combine.hpp (two streams merged by a rule; pool_sx .. pool_plane_words are then the decoder's own)
 	const uint32_t* pool_cut = nullptr;
 	const uint64_t* pool_off = nullptr;
 	const uint64_t* pool_label = nullptr;

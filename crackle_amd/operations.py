@@ -5,7 +5,8 @@ array_equal, mode_pooling_2x2x1, point_cloud, contacts, overlaps, connected_comp
 The label edits remap, mask and mask_except rewrite header and label section on the host; recompress
 re-encodes a stream from its own labels on the device (ckl_recompress), without decoding a voxel.  erode and dilate
 take the same road with the eroded or dilated labels at its end (ckl_erode, ckl_dilate); opening and closing are one
-after the other.  downsample takes it with the pooled labels, and a smaller volume, at its end (ckl_downsample)."""
+after the other.  downsample takes it with the pooled labels, and a smaller volume, at its end (ckl_downsample).
+overlay and mask_by take it with two streams of one shape at its start and a rule on their labels (ckl_combine)."""
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -764,6 +765,76 @@ def downsample(
     binary = _reencode("downsample", "ckl_downsample", binary, (*f, 0), markov_model_order, device)
     levels.append(binary)
   return levels
+
+
+def _combine(what: str, rule: int, binary: bytes, other: bytes, markov_model_order: Optional[int], device: int) -> bytes:
+  """The call that overlay and mask_by share (ckl_combine), after the refusals the host decides."""
+  from .codec import _raise
+  a, b = bytes(binary), bytes(other)
+  ha, hb = header(a), header(b)
+  if (ha.sx, ha.sy, ha.sz) != (hb.sx, hb.sy, hb.sz):
+    raise ValueError(
+      f"{what}: the volumes differ in shape: {ha.sx} x {ha.sy} x {ha.sz} and {hb.sx} x {hb.sy} x {hb.sz}")
+  if ha.signed or hb.signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  _checked_order(what, markov_model_order)
+  order = -1 if markov_model_order is None else int(markov_model_order)
+  out, n = C.c_void_p(), C.c_uint64()
+  rc = _lib.lib().ckl_combine(a, len(a), b, len(b), int(rule), 0, order, int(device), C.byref(out), C.byref(n))
+  if rc != _lib.CKL_OK:
+    _raise(rc)
+  return _take(out, n)
+
+
+def overlay(binary: bytes, other: bytes, markov_model_order: Optional[int] = None, device: int = 0) -> bytes:
+  """compress(V, markov_model_order=m), byte for byte, where V = B where B != 0, else A, with A = decompress(binary)
+  and B = decompress(other): the objects of `other` put on top of `binary`, without the voxels of either (the
+  reference has none).  overlay(other, binary) is the other direction: A's background filled from B.
+
+  The two streams must agree in shape (ValueError otherwise) and may differ in everything else: dtype, FLAT or pin
+  labels, format version, crack format, markov order, memory order, unsorted or merged label lists.  Label 0 of
+  `other` is the only special value.  Equality is by label: the false boundaries that remap, mask, dust or fill_holes
+  leave in either stream change nothing.
+
+  V has the unsigned dtype whose width is the larger of the two streams' data widths.  m is binary's order unless
+  markov_model_order is given, and the fortran_order flag is binary's.  The output has FLAT labels, format version 1,
+  whatever the inputs had, the crack format the combined volume itself selects, and the stored width of the largest
+  label that survives; when nothing survives it is the stream of an all-zero volume, as erode() documents.
+
+  On the device both decoders run up to their run tables, side by side; no dense label volume exists: a row can
+  change its combined label only where one of the two streams has a break, the rule is evaluated there with one
+  label fetch per run of either stream, the encoder's planes are written from those labelled cuts by downsample()'s
+  own kernel, and the encoder's crack and label stages follow as for recompress (ckl_combine.hpp).  Signed streams
+  raise TypeError, a negative order ValueError; a damaged slice raises what decompress raises for that stream,
+  binary's first; streams without voxels come back as the header-only stream of their shape, without a device, as
+  recompress returns it.
+
+  Not done: where(cond, a, b) over three streams, a joint (product) segmentation with fresh ids, a fill value other
+  than 0, z-ranges, a sharded version, a place in the thread-job and stream-kind matrices of the existing test
+  files."""
+  return _combine("overlay", _lib.CKL_COMBINE_OVERLAY, binary, other, markov_model_order, device)
+
+
+def mask_by(binary: bytes, other: bytes, invert: bool = False, markov_model_order: Optional[int] = None, device: int = 0) -> bytes:
+  """compress(V, markov_model_order=m), byte for byte, where V = A where (B != 0) != invert, else 0, with
+  A = decompress(binary) and B = decompress(other): `binary` cut down to the mask that `other` is (invert: to what
+  lies outside it), without the voxels of either (the reference has none).
+
+  The two streams must agree in shape (ValueError otherwise) and may differ in everything else, as overlay()
+  documents.  other's labels never appear in the result, only whether they are 0.  Equality is by label: false
+  boundaries in either stream change nothing.
+
+  The data width, the fortran_order flag and the default m are binary's.  The output has FLAT labels, format version
+  1, whatever the inputs had, the crack format the combined volume itself selects, and the stored width of the
+  largest label that survives; when nothing survives it is the stream of an all-zero volume, as erode() documents.
+
+  The device side, the refusals, damaged slices and streams without voxels are overlay()'s (ckl_combine.hpp).
+
+  Not done: where(cond, a, b) over three streams, a joint (product) segmentation with fresh ids, a fill value other
+  than 0, z-ranges, a sharded version, a place in the thread-job and stream-kind matrices of the existing test
+  files."""
+  rule = _lib.CKL_COMBINE_DROP_WHERE if invert else _lib.CKL_COMBINE_KEEP_WHERE
+  return _combine("mask_by", rule, binary, other, markov_model_order, device)
 
 
 def opening(

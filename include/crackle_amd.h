@@ -573,6 +573,28 @@ int ckl_dilate(const uint8_t* buf, uint64_t n, int connectivity, int flags, int 
 int ckl_downsample(const uint8_t* buf, uint64_t n, int fx, int fy, int fz, int flags, int markov_model_order, int device,
                    uint8_t** out, uint64_t* out_len);
 
+/* Two streams of one shape merged by a rule on their labels (the reference has none): the stream that ckl_compress gives
+ * for the combined volume, written as ckl_erode writes its own (FLAT labels, format version 1, markov_model_order < 0:
+ * keep a's, a's fortran_order flag; the crack format is the one the combined volume itself selects).  With a and b the
+ * labels of buf_a and buf_b at a voxel, b mattering only as "is it 0":
+ *   CKL_COMBINE_OVERLAY      b != 0 ? b : a    the data width is the larger of the two streams'
+ *   CKL_COMBINE_KEEP_WHERE   b != 0 ? a : 0    a's data width; b's labels never appear
+ *   CKL_COMBINE_DROP_WHERE   b != 0 ? 0 : a    likewise
+ * The streams may differ in everything but shape: data width, FLAT or pin labels, format version, crack format, markov
+ * order, memory order.  No voxel is decoded and no dense label volume exists: both decoders run up to their run tables
+ * on the one device, the words are cut where either stream's row has a break (k_combine_cuts), the rule is evaluated
+ * once per cut with one run cursor per stream (k_combine_labels), the encoder's planes are written from those labelled
+ * cuts by ckl_downsample's own kernel (k_pool_planes), and the encoder's crack and label stages follow, the label stage
+ * reading the cuts.  `flags` must be 0.  Streams of different shapes, signed streams, an unknown rule and flags other
+ * than 0 are CKL_ERR_ARG; streams without voxels become the header-only stream of their shape, without a device.  A
+ * damaged slice fails as in ckl_decompress, buf_a's first.  *out is released with ckl_free. */
+#define CKL_COMBINE_OVERLAY     0
+#define CKL_COMBINE_KEEP_WHERE  1   /* mask_by */
+#define CKL_COMBINE_DROP_WHERE  2   /* mask_by(invert=True) */
+int ckl_combine(const uint8_t* buf_a, uint64_t n_a, const uint8_t* buf_b, uint64_t n_b,
+                int rule, int flags /* must be 0 */, int markov_model_order /* -1: a's */, int device,
+                uint8_t** out, uint64_t* out_len);
+
 /* Native form of crackle.operations.zsplit's range helper (crackle/operations.py:550-623):
  * the stream of slices [z_start, z_end) of a FLAT stream, without decoding (host only).
  * *out is released with ckl_free. */

@@ -3,10 +3,12 @@ stream behind numpy-style indexing (the reference's CrackleArray.__getitem__, cr
 which decodes the whole slices of the z-range and lets numpy crop them).  Here the device writes the
 box alone (ckl_cutout: the decode pipeline up to the run tables, then k_paint_window) and only the box
 crosses the link.  paste() is the way back (the reference's __setitem__, crackle/array.py:287-340):
-the slices of the box's z-range are decoded, edited and encoded again in HBM (ckl_paste)."""
+the slices of the box's z-range are decoded, edited and encoded again in HBM (ckl_paste).  crop(), crop_boxes()
+and chunks() give boxes as streams of their own, from the run tables of one decode and without a voxel
+(ckl_crop_boxes)."""
 import ctypes as C
 import operator
-from typing import List, Optional, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -177,6 +179,99 @@ def paste(binary: bytes, slices, data, device: int = 0) -> bytes:
   return operations._take(out, n)
 
 
+def crop_boxes(binary: bytes, boxes, markov_model_order: Optional[int] = None, device: int = 0) -> List[bytes]:
+  """One stream per index expression of `boxes`, in order, each exactly what crop() gives for that box, with the
+  stream decoded ONCE for all of them (ckl_crop_boxes).  Boxes may overlap, repeat, differ in shape and stand in any
+  order; an empty sequence gives an empty list.
+
+  On the device one decode session runs up to its run tables over the slices [min z0, max z1) of the boxes that hold
+  voxels, and one label per run is gathered once.  Every box then takes a turn: its words are cut where the input row
+  under them has a break, the labels at those cuts are read through the runs, downsample()'s own kernel writes the
+  encoder's planes from them, and the encoder's crack and label stages follow for the box's shape (ckl_crop.hpp).
+  Boxes of one shape share an encode session.  No voxel of the input or of a box exists anywhere.
+
+  A damaged slice inside [min z0, max z1) raises what decompress_range raises for it, whichever box is asked for,
+  and nothing is returned; a damaged slice outside that range is never looked at.  Index errors are cutout()'s
+  (normalize_index), a step other than 1 and a negative order are ValueError, signed streams TypeError; all of them
+  are raised before any device work, for every box.  Boxes with an axis of size 0 become the 29-byte header-only
+  stream of their shape, on the host."""
+  binary = bytes(binary)
+  head = CrackleHeader.frombytes(binary)
+  if head.signed:
+    raise TypeError("Signed integer data types are not currently supported.")
+  operations._checked_order("crop", markov_model_order)
+  flat = []
+  for expr in boxes:
+    idx = normalize_index(expr, (head.sx, head.sy, head.sz))
+    for start, stop, step, _ in idx:
+      if step != 1:
+        raise ValueError(f"crop: steps other than 1 are not supported (strided subsampling is not a crop). Got: {step}")
+      flat.extend((start, stop))
+  n_boxes = len(flat) // 6
+  if n_boxes == 0:
+    return []
+  order = -1 if markov_model_order is None else int(markov_model_order)
+  outs, lens = (C.c_void_p * n_boxes)(), (C.c_uint64 * n_boxes)()
+  rc = _lib.lib().ckl_crop_boxes(
+    binary, len(binary), (C.c_int64 * len(flat))(*flat), n_boxes, 0, order, int(device),
+    C.cast(outs, C.POINTER(C.c_void_p)), C.cast(lens, C.POINTER(C.c_uint64)),
+  )
+  if rc != _lib.CKL_OK:
+    codec._raise(rc)
+  return [operations._take(C.c_void_p(outs[k]), C.c_uint64(lens[k])) for k in range(n_boxes)]
+
+
+def crop(binary: bytes, slices, markov_model_order: Optional[int] = None, device: int = 0) -> bytes:
+  """The box ``decompress(binary)[slices]`` as a stream of its own: compress(V, markov_model_order=m), byte for byte,
+  where V is the contiguous copy of the box in the memory order of the input's fortran_order flag, without the voxels
+  of the input or of the box (the reference has none; cutout() gives the box as voxels, paste() is the way back).
+
+  `slices` means what it means for cutout() (normalize_index, the same errors), with two differences: an int index
+  keeps its axis at size 1, because a stream is always three-dimensional, and a step other than 1 is ValueError.
+  m is the input's order unless markov_model_order is given.  The output has FLAT labels, format version 1, whatever
+  the input had (FLAT, pins, version 0), the input's data width and fortran_order flag, and the crack format, stored
+  width and key widths that the box itself selects: a box can lose the input's largest label.  The box that is the
+  whole volume gives recompress(binary); a box with an axis of size 0 gives the 29-byte header-only stream of its
+  shape, on the host, as recompress gives it for a volume without voxels.
+
+  The device side, damaged slices (one inside the box's z-range raises what decompress_range raises for it, one
+  outside is never looked at) and the refusals are crop_boxes()'s, of which this is the call with one box.
+
+  Not done: steps other than 1, joining streams along x or y, a sharded version, a place in the thread-job and
+  stream-kind matrices of the existing test files."""
+  return crop_boxes(binary, [slices], markov_model_order=markov_model_order, device=device)[0]
+
+
+def chunk_boxes(shape, chunk_size) -> List[Tuple[int, int, int, int, int, int]]:
+  """The boxes (x0, x1, y0, y1, z0, z1) of the grid of chunks of `chunk_size` = (cx, cy, cz) that tiles a volume of
+  `shape` from (0, 0, 0), in x-fastest grid order; chunks at the far faces are smaller.  Pure arithmetic.  A volume
+  with an axis of size 0 has no chunks; a chunk size below 1 is ValueError."""
+  try:
+    size = tuple(operator.index(c) for c in chunk_size)
+  except TypeError:
+    size = ()
+  if len(size) != 3 or min(size) < 1:
+    raise ValueError(f"chunks: chunk_size must be three integers of at least 1. Got: {chunk_size}")
+  sx, sy, sz = (int(s) for s in shape)
+  cx, cy, cz = size
+  return [
+    (x0, min(x0 + cx, sx), y0, min(y0 + cy, sy), z0, min(z0 + cz, sz))
+    for z0 in range(0, sz, cz) for y0 in range(0, sy, cy) for x0 in range(0, sx, cx)
+  ]
+
+
+def chunks(binary: bytes, chunk_size, markov_model_order: Optional[int] = None, device: int = 0) -> Dict[Tuple[int, int, int], bytes]:
+  """{(x0, y0, z0): stream} of the grid of chunks of `chunk_size` that tiles the volume from (0, 0, 0) (chunk_boxes),
+  in x-fastest grid order: what a level of a downsample() pyramid is stored as.  Each stream is what crop() gives for
+  its box, and the input is decoded once for all of them (crop_boxes); a grid has at most eight shapes of box, so at
+  most eight encode sessions serve it."""
+  binary = bytes(binary)
+  head = CrackleHeader.frombytes(binary)
+  grid = chunk_boxes((head.sx, head.sy, head.sz), chunk_size)
+  streams = crop_boxes(binary, [(slice(b[0], b[1]), slice(b[2], b[3]), slice(b[4], b[5])) for b in grid], markov_model_order=markov_model_order, device=device)
+  return {(b[0], b[2], b[4]): s for b, s in zip(grid, streams)}
+
+
 class CrackleArray:
   """A stream behind an array interface (crackle/array.py:32-340): metadata from the header and the
   label section, ``arr[x0:x1, y0:y1, z0:z1]`` through cutout(), ``arr.paste(slices, data)`` for the
@@ -239,6 +334,16 @@ class CrackleArray:
   # (no __setitem__: tests/test_cutout_cpu.py pins that the array is never edited in place)
   def paste(self, slices, data) -> "CrackleArray":
     return CrackleArray(paste(self.binary, slices, data, device=self.device), self.device)
+
+  def crop(self, slices) -> "CrackleArray":
+    """The box as an array of its own (crop): an int index keeps its axis at size 1."""
+    return CrackleArray(crop(self.binary, slices, device=self.device), self.device)
+
+  def crop_boxes(self, boxes) -> List["CrackleArray"]:
+    return [CrackleArray(b, self.device) for b in crop_boxes(self.binary, boxes, device=self.device)]
+
+  def chunks(self, chunk_size) -> Dict[Tuple[int, int, int], "CrackleArray"]:
+    return {key: CrackleArray(b, self.device) for key, b in chunks(self.binary, chunk_size, device=self.device).items()}
 
   def voxel_counts(self, label: Optional[int] = None):
     return codec.voxel_counts(self.binary, label=label, device=self.device)

@@ -1,10 +1,11 @@
 // crackle.operations.recompress (crackle/operations.py:664-857 decodes slabs to voxels and compresses them again), and
-// erode, dilate, downsample and combine, which are the same road with another volume at its end (combine: of two streams,
-// through a sibling of recompress() below).  Here no voxel exists anywhere:
+// erode, dilate, downsample, combine and crop, which are the same road with another volume at its end (combine: of two
+// streams, through a sibling of recompress() below; crop: many volumes, the boxes of one call, from one TABLES run,
+// through crop_boxes() below).  Here no voxel exists anywhere:
 // a TABLES run of the decoder leaves the runs of every slice and the label of every component, a plane stage writes the
 // encoder's planes and their counts from them (plain: ckl_recompress.hpp, eroded: ckl_erode.hpp, dilated:
 // ckl_dilate.hpp, pooled: ckl_downsample.hpp, the one whose volume has another shape than the decoder's, combined:
-// ckl_combine.hpp, the one with two decoders), and
+// ckl_combine.hpp, the one with two decoders, cropped: ckl_crop.hpp, the one with many encoders), and
 // encode_from_planes (ckl_encoder.hpp) goes on as the encoder does from cached planes, with its label stage reading the
 // same tables.  The bytes are those of compress(edit(decompress(stream)), markov_model_order).
 #include "ckl_encoder.hpp"
@@ -14,9 +15,12 @@
 #include "ckl_dilate.hpp"
 #include "ckl_downsample.hpp"
 #include "ckl_combine.hpp"
+#include "ckl_crop.hpp"
 
 #include <algorithm>
 #include <chrono>
+#include <map>
+#include <tuple>
 
 using namespace ckl;
 using namespace ckl::dev;
@@ -25,7 +29,7 @@ namespace {
 
 // what a call does to the labels on their way through
 struct LabelEdit {
-	enum Kind { NONE, ERODE, DILATE, POOL, COMBINE } kind = NONE;
+	enum Kind { NONE, ERODE, DILATE, POOL, COMBINE, CROP } kind = NONE;
 	int connectivity = 0;          // ERODE, DILATE: 6, 18, 26
 	bool keep_border = false;      // ERODE: neighbours outside the volume are ignored
 	int fx = 1, fy = 1, fz = 1;    // POOL: (2, 2, 1) or (2, 2, 2)
@@ -40,6 +44,7 @@ constexpr EditNames kEditNames[] = {
 	{ "dilate", "gain_planes", "k_dilate_device" },
 	{ "downsample", "pool_planes", "k_pool_device" },
 	{ "combine", "merge_planes", "k_combine_device" },
+	{ "crop", "crop_planes", "k_crop_device" },
 };
 
 // Device scratch of one call's edit.  What a plane stage returns points into it and is read by the encoder's label
@@ -52,7 +57,8 @@ struct EditScratch {
 	DevBuf<uint32_t> pool_cut;                 // ckl_downsample.hpp's plane of cuts, [osz][output plane_words]
 	DevBuf<uint64_t> pool_cut_off;             // [osz][output plane_words]
 	DevBuf<uint64_t> pool_label;               // [cuts]
-	// (ckl_combine.hpp's cuts, their offsets and labels stand in the three pool_* buffers: the same triple at the volume's own shape)
+	// (ckl_combine.hpp's cuts, their offsets and labels stand in the three pool_* buffers: the same triple at the volume's own
+	// shape; ckl_crop.hpp's likewise, at the shape of the box whose turn it is)
 };
 
 // what the plane stages launch with
@@ -62,7 +68,7 @@ struct Road {
 	hipStream_t s;                     // the encode session's
 	uint32_t ns;                       // the ENCODER's slices (POOL: not the decoder's)
 	dim3 word_grid;                    // a thread per 32-pixel word of the encoder's planes
-	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's, ckl_downsample's and ckl_combine's cursor
+	unsigned long long* counters;      // zeroed: [0] the largest label, [1] ckl_dilate's, ckl_downsample's, ckl_combine's and ckl_crop's cursor
 };
 
 // the decode session's tables as the kernels of this road read them
@@ -154,6 +160,24 @@ void combined_planes(const Road& r, RunLabels& src, const CombineSide& a, const 
 	hipLaunchKernelGGL(k_pool_planes, r.word_grid, dim3(kBlock), 0, r.s, src, same, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
 }
 
+// Returns the number of cuts and leaves the box's triple in src (a copy of the session's tables for this box; the label
+// stage reads the triple alone); counters[0] takes the largest label of the box.  The word grid, the planes and the counts
+// are the box's, the tables behind src are the session's.
+unsigned long long cropped_planes(const Road& r, RunLabels& src, const uint64_t* run_label, const CropBox& box, EditScratch& scratch) {
+	const PoolGeom& p = box.p;
+	const size_t pw = p.plane_words * r.ns;
+	scratch.pool_cut.ensure(pw);
+	scratch.pool_cut_off.ensure(pw);
+	hipLaunchKernelGGL(k_crop_cuts, r.word_grid, dim3(kBlock), 0, r.s, src.g, box, scratch.pool_cut.p, scratch.pool_cut_off.p, r.counters + 1);
+	const unsigned long long cuts = download(r.counters + 1, 1, r.s)[0];      // the host sizes the cuts' labels (every word has a cut: not 0)
+	scratch.pool_label.ensure(cuts);
+	hipLaunchKernelGGL(k_crop_labels, r.word_grid, dim3(kBlock), 0, r.s, src, run_label, box, scratch.pool_cut.p, scratch.pool_cut_off.p, scratch.pool_label.p, r.counters);
+	src.pool_cut = scratch.pool_cut.p; src.pool_off = scratch.pool_cut_off.p; src.pool_label = scratch.pool_label.p;
+	src.pool_sx = p.sx; src.pool_sy = p.sy; src.pool_row_words = p.row_words; src.pool_plane_words = p.plane_words;
+	hipLaunchKernelGGL(k_pool_planes, r.word_grid, dim3(kBlock), 0, r.s, src, p, plane_v(r.e), plane_h(r.e, r.ns), r.e.d_count_vh.p, r.ns);
+	return cuts;
+}
+
 // lib::pixel_pairs (lib.hpp:249-256): equal neighbours in x-fastest order — inside the rows every pair that V does not
 // mark, and the wrap-arounds the plane writer counted.  counts: [3][ns] bits of V | bits of H | wrap pairs
 VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_label, int64_t sx, int64_t sy, uint32_t ns) {
@@ -163,8 +187,8 @@ VolumeStats stats_from_counts(const std::vector<uint32_t>& counts, uint64_t max_
 	return st;
 }
 
-// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the five operations read it).  extra: DILATE's
-// gained pixels, POOL's and COMBINE's pieces
+// the call's line under CKL_PROFILE (tools/*_timing.py and the GPU tests of the six operations read it; CROP: one line per
+// box).  extra: DILATE's gained pixels, POOL's, COMBINE's and CROP's pieces
 void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, const ckl_encoder& e, float ms_kernel, unsigned long long extra) {
 	double graph = 0, cracks = 0, labels = 0, assembly = 0;
 	for (const auto& m : e.host_marks) {
@@ -177,7 +201,7 @@ void print_profile(const LabelEdit& edit, double ms_tables, double ms_planes, co
 	const EditNames& names = kEditNames[edit.kind];
 	char tail[40] = "";
 	if (edit.kind == LabelEdit::DILATE) snprintf(tail, sizeof(tail), " gained=%llu", extra);
-	if (edit.kind == LabelEdit::POOL || edit.kind == LabelEdit::COMBINE) snprintf(tail, sizeof(tail), " pieces=%llu", extra);
+	if (edit.kind == LabelEdit::POOL || edit.kind == LabelEdit::COMBINE || edit.kind == LabelEdit::CROP) snprintf(tail, sizeof(tail), " pieces=%llu", extra);
 	fprintf(stderr, "[ckl %s host ms] tables=%.2f %s=%.2f graph=%.2f cracks=%.2f labels=%.2f assembly=%.2f %s=%.3f%s\n",
 		names.op, ms_tables, names.planes_field, ms_planes, graph, cracks, labels, assembly, names.device_field, ms_kernel, tail);
 }
@@ -200,10 +224,11 @@ Header checked_header(const uint8_t* buf, uint64_t n, int markov_order, const La
 	return head;
 }
 
-// a decode session of the whole stream after its TABLES run (a damaged slice raises here, as for a decode)
-DecoderPtr tables_session(const uint8_t* buf, uint64_t n, int device) {
+// a decode session of the whole stream (or of its slices [z_start, z_end)) after its TABLES run (a damaged slice of the
+// session raises here, as for a decode; one outside it is never looked at)
+DecoderPtr tables_session(const uint8_t* buf, uint64_t n, int device, int64_t z_start = 0, int64_t z_end = -1) {
 	DecoderPtr dec;
-	const int rc = open_decoder(buf, n, 0, -1, device, dec);
+	const int rc = open_decoder(buf, n, z_start, z_end, device, dec);
 	if (rc != CKL_OK) throw Error(rc, ckl_last_error());
 	enter(dec.get());
 	decoder_run(*dec, { Goal::TABLES });
@@ -343,6 +368,115 @@ void combine(const uint8_t* buf_a, uint64_t n_a, const uint8_t* buf_b, uint64_t 
 	if (getenv("CKL_PROFILE")) print_profile(edit, ms_between(t_start, t_tables), ms_between(t_tables, t_planes), e, ms_kernel, pieces);
 }
 
+// a box of a crop call: [x0, x1) x [y0, y1) x [z0, z1) of the stream's volume
+struct Box {
+	int64_t x0, x1, y0, y1, z0, z1;
+	int64_t wx() const { return x1 - x0; }
+	int64_t wy() const { return y1 - y0; }
+	int64_t wz() const { return z1 - z0; }
+	bool empty() const { return wx() == 0 || wy() == 0 || wz() == 0; }
+};
+
+// recompress()'s sibling for many outputs: one stream per box, each the stream compress() gives for the box's voxels.
+// One decode session over the z-range that the boxes with voxels span, one TABLES run and one label per run for all of
+// them; then a turn per box through ckl_crop.hpp's kernels and the encoder.  Boxes of one shape share an encode session.
+// outs / out_lens: n_boxes entries, null / 0 on entry; whoever calls frees what stands there when this throws.
+void crop_boxes(const uint8_t* buf, uint64_t n, const Box* boxes, uint64_t n_boxes, int markov_order, int device, uint8_t** outs, uint64_t* out_lens) {
+	LabelEdit edit;
+	edit.kind = LabelEdit::CROP;
+	uint64_t order = 0;
+	const Header head = checked_header(buf, n, markov_order, edit, order);
+	// every box is checked before any device work
+	for (uint64_t k = 0; k < n_boxes; k++) {
+		check_box_axis("crop", "x", boxes[k].x0, boxes[k].x1, head.sx);
+		check_box_axis("crop", "y", boxes[k].y0, boxes[k].y1, head.sy);
+		check_box_axis("crop", "z", boxes[k].z0, boxes[k].z1, head.sz);
+	}
+	// boxes without voxels are the host's: the header-only stream of their shape
+	int64_t zmin = INT64_MAX, zmax = -1;
+	for (uint64_t k = 0; k < n_boxes; k++) {
+		const Box& b = boxes[k];
+		if (b.empty()) hand_out(header_bytes(stream_header(head.data_width, b.wx(), b.wy(), b.wz(), VolumeStats(), false, head.fortran_order, order, nullptr)), OutAlloc::MALLOC, outs + k, out_lens + k);
+		else { zmin = std::min(zmin, b.z0); zmax = std::max(zmax, b.z1); }
+	}
+	if (zmax < 0) return;
+	select_device(device);      // (what came before needs none)
+	const auto t_start = Clock::now();
+	const DecoderPtr dec = tables_session(buf, n, device, zmin, zmax);      // (a damaged slice of [zmin, zmax) raises here, whichever box is asked for)
+	ckl_decoder& d = *dec;
+	if (d.nslices != static_cast<uint32_t>(zmax - zmin)) throw Error(CKL_ERR_RUNTIME, "crackle_amd: crop: the session's slices are not the boxes' z-range");
+	const RunLabels tables = run_labels(d);
+	const uint64_t* run_label = gather_run_labels(d, tables, d.stream);
+	CKL_HIP(hipStreamSynchronize(d.stream));      // (the encode sessions' streams do not wait for the decoder's)
+	double ms_tables = ms_between(t_start, Clock::now());
+
+	DevBuf<unsigned long long> counters;
+	counters.ensure(2);
+	EditScratch scratch;
+	std::map<std::tuple<int64_t, int64_t, int64_t>, EncoderPtr> sessions;      // one per shape of box
+	for (uint64_t k = 0; k < n_boxes; k++) {
+		const Box& b = boxes[k];
+		if (b.empty()) continue;
+		const auto t_box = Clock::now();
+		const int64_t sx = b.wx(), sy = b.wy(), sz = b.wz();
+		EncoderPtr& enc = sessions[std::make_tuple(sx, sy, sz)];
+		if (!enc) {
+			ckl_encoder* raw = nullptr;
+			if (ckl_encoder_create(sx, sy, sz, head.data_width, device, &raw) != CKL_OK) throw Error(CKL_ERR_RUNTIME, ckl_last_error());
+			enc.reset(raw);
+		}
+		ckl_encoder& e = *enc;
+		enter(&e);
+		const uint32_t ns = static_cast<uint32_t>(sz);
+		const uint32_t row_words = static_cast<uint32_t>((sx + 31) / 32);
+		const uint64_t plane_words = static_cast<uint64_t>(row_words) * sy;
+		planes_adopt(e, row_words, plane_words, ns, 3);
+		CKL_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), e.stream));
+		const Road r = { d, e, e.stream, ns, dim3(static_cast<uint32_t>((plane_words + kBlock - 1) / kBlock), ns), counters.p };
+		const CropBox box = { static_cast<uint32_t>(b.x0), static_cast<uint32_t>(b.y0), static_cast<uint32_t>(b.z0 - zmin),
+			{ 1u, ns, static_cast<uint32_t>(sx), static_cast<uint32_t>(sy), row_words, plane_words } };
+		RunLabels src = tables;
+		CKL_HIP(hipEventRecord(e.evd0, r.s));
+		cropped_planes(r, src, run_label, box, scratch);
+		CKL_HIP(hipEventRecord(e.evd1, r.s));
+		const std::vector<uint32_t> counts = download(e.d_count_vh.p, 3 * static_cast<size_t>(ns), r.s);
+		const VolumeStats st = stats_from_counts(counts, download(counters.p, 1, r.s)[0], sx, sy, ns);      // (k_crop_labels has taken the box's largest label)
+		float ms_kernel = 0.f;
+		CKL_HIP(hipEventElapsedTime(&ms_kernel, e.evd0, e.evd1));
+		const auto t_planes = Clock::now();
+
+		encode_from_planes(e, src, sx, sy, sz, head.data_width, head.fortran_order, order, st, counts, outs + k, out_lens + k);
+		// the box's runs, counted as POOL and COMBINE count their pieces: one per row and one more per bit of V
+		unsigned long long pieces = static_cast<unsigned long long>(sy) * ns;
+		for (uint32_t zi = 0; zi < ns; zi++) pieces += counts[zi];
+		if (getenv("CKL_PROFILE")) print_profile(edit, ms_tables, ms_between(t_box, t_planes), e, ms_kernel, pieces);
+		ms_tables = 0;      // (the shared run stands on the first box's line)
+	}
+}
+
+// the C entry of crop_boxes: boxes as [n_boxes][6] x0 x1 y0 y1 z0 z1; on any error every stream already handed out is
+// freed and all of outs are left null
+void crop_entry(const uint8_t* buf, uint64_t n, const int64_t* boxes, uint64_t n_boxes, int flags, int markov_order, int device, uint8_t** outs, uint64_t* out_lens) {
+	if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: crop: flags must be 0");
+	if (n_boxes == 0) return;
+	if (!buf || !boxes || !outs || !out_lens) throw Error(CKL_ERR_ARG, "crackle_amd: null argument");
+	std::vector<Box> bx(n_boxes);
+	for (uint64_t k = 0; k < n_boxes; k++) {
+		bx[k] = { boxes[6 * k], boxes[6 * k + 1], boxes[6 * k + 2], boxes[6 * k + 3], boxes[6 * k + 4], boxes[6 * k + 5] };
+		outs[k] = nullptr; out_lens[k] = 0;
+	}
+	try {
+		crop_boxes(buf, n, bx.data(), n_boxes, markov_order, device, outs, out_lens);
+	}
+	catch (...) {
+		for (uint64_t k = 0; k < n_boxes; k++) {
+			if (outs[k]) ckl_free(outs[k]);
+			outs[k] = nullptr; out_lens[k] = 0;
+		}
+		throw;
+	}
+}
+
 }  // namespace
 
 extern "C" {
@@ -386,6 +520,18 @@ int ckl_combine(const uint8_t* buf_a, uint64_t n_a, const uint8_t* buf_b, uint64
 		if (flags) throw Error(CKL_ERR_ARG, "crackle_amd: combine: flags must be 0");
 		combine(buf_a, n_a, buf_b, n_b, rule, markov_model_order, device, out, out_len);
 	});
+}
+
+int ckl_crop_boxes(const uint8_t* buf, uint64_t n, const int64_t* boxes, uint64_t n_boxes, int flags, int markov_model_order, int device, uint8_t** outs, uint64_t* out_lens) {
+	return guard([&] { crop_entry(buf, n, boxes, n_boxes, flags, markov_model_order, device, outs, out_lens); });
+}
+
+int ckl_crop(
+	const uint8_t* buf, uint64_t n, int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1,
+	int flags, int markov_model_order, int device, uint8_t** out, uint64_t* out_len
+) {
+	const int64_t box[6] = { x0, x1, y0, y1, z0, z1 };
+	return ckl_crop_boxes(buf, n, box, 1, flags, markov_model_order, device, out, out_len);
 }
 
 }  // extern "C"

@@ -595,6 +595,34 @@ int ckl_combine(const uint8_t* buf_a, uint64_t n_a, const uint8_t* buf_b, uint64
                 int rule, int flags /* must be 0 */, int markov_model_order /* -1: a's */, int device,
                 uint8_t** out, uint64_t* out_len);
 
+/* An x, y, z box of a stream as a stream of its own (the reference has none; ckl_cutout gives the box as voxels): the
+ * stream that ckl_compress gives for the voxels [x0, x1) x [y0, y1) x [z0, z1) of the decoded volume, written as
+ * ckl_erode writes its own (FLAT labels, format version 1, markov_model_order < 0: keep the input's, the input's data
+ * width and fortran_order flag; the crack format, the stored width and the key widths are the ones the box itself
+ * selects).  ckl_crop_boxes gives one stream per box, in order, each exactly what ckl_crop gives for that box, and decodes
+ * the stream ONCE for all of them; ckl_crop is ckl_crop_boxes with one box.
+ *   boxes     [n_boxes][6]: x0 x1 y0 y1 z0 z1.  Boxes may overlap, repeat and stand in any order.
+ *   outs      [n_boxes] streams, each released with ckl_free; out_lens [n_boxes] their lengths
+ * Bounds as for ckl_cutout: 0 <= x0 <= x1 <= sx and likewise y and z, else CKL_ERR_ARG with the axis in ckl_last_error;
+ * nothing is clamped, and every box is checked before any device work.  A box with an axis of size 0 becomes the
+ * header-only stream of its shape, without a device; the box that is the whole volume gives what ckl_recompress gives.
+ * n_boxes == 0 is CKL_OK and touches nothing.  `flags` must be 0; flags other than 0 and signed streams are CKL_ERR_ARG.
+ * No voxel is decoded and no dense label volume exists, neither the input's nor a box's: one decode session runs up to
+ * its run tables over the slices [min z0, max z1) of the boxes with voxels, one label per run is gathered once, and
+ * every box then takes a turn: its words are cut where the input row under them has a break (k_crop_cuts), the labels
+ * at the cuts are read through the runs (k_crop_labels), the encoder's planes are written from those labelled cuts by
+ * ckl_downsample's own kernel (k_pool_planes), and the encoder's crack and label stages follow for the BOX's shape.
+ * Boxes of one shape share an encode session.  A damaged slice inside [min z0, max z1) fails as in ckl_decompress,
+ * whichever box is asked for; one outside that range is never looked at.  On any error every stream already handed
+ * out is freed and all of outs are left null. */
+int ckl_crop(const uint8_t* buf, uint64_t n,
+             int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1,
+             int flags /* must be 0 */, int markov_model_order /* -1: the stream's */, int device,
+             uint8_t** out, uint64_t* out_len);
+int ckl_crop_boxes(const uint8_t* buf, uint64_t n, const int64_t* boxes /* [n_boxes][6]: x0 x1 y0 y1 z0 z1 */, uint64_t n_boxes,
+                   int flags /* must be 0 */, int markov_model_order /* -1: the stream's */, int device,
+                   uint8_t** outs, uint64_t* out_lens);
+
 /* Native form of crackle.operations.zsplit's range helper (crackle/operations.py:550-623):
  * the stream of slices [z_start, z_end) of a FLAT stream, without decoding (host only).
  * *out is released with ckl_free. */
